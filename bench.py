@@ -12,9 +12,12 @@ The graph is the reference's own RMAT generator (graph_gen.cc:159-287, seed 1997
 .57,.19,.19, edge factor 16, permute=true) run on the device, then do_semi_sort +
 make_reverse_edges exactly as load_binary does.  Total work is fixed as N grows ("strong").
 
-Rank 0 prints ONE JSON line with the driver's contract fields plus `roofline`, `cpu_baseline` and, at N = 1,
-`extra`: the other BASELINE.json configurations measured in the same run (PageRank fp64 on the same graph,
-PageRank fp32 on RMAT-24, hop_dist from vertex 0 on RMAT-26, triangle counting on symmetrised RMAT-24).
+Rank 0 prints ONE JSON line with the driver's contract fields plus `roofline` (from the timed steps themselves).
+A plain run does only that.  With --full, at N = 1, the line also holds `roofline.copy_bw_gbs` (a device copy timed
+on its own), `cpu_baseline` and `extra`: the other BASELINE.json configurations measured in the same run (PageRank
+fp64 on the same graph, PageRank fp32 on RMAT-24, hop_dist from vertex 0 on RMAT-26, triangle counting on
+symmetrised RMAT-24).  --dump-outputs DIR writes what the last timed step computed (a fixed sample of rank[] and
+the step's diff) as .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -25,15 +28,14 @@ import statistics
 import sys
 import time
 
-# the CPU baseline pins its OpenMP threads like the reference's run.sh does (scripts/run.sh:237-238,350);
-# libgomp reads this once, when it is first loaded
-os.environ.setdefault("GOMP_CPU_AFFINITY", "0-%d" % ((os.cpu_count() or 1) - 1))
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "green-marl_amd"))
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 
+
+# --dump-outputs: rank[] at this many vertices, drawn with a fixed seed (the whole vector at RMAT-26 is 256 MB)
+DUMP_SAMPLE = 1 << 20
 
 # the sources of the kernels of one PageRank step (the bench line's roofline kernels) and of the plan they run on
 STEP_SOURCES = ("gmx_pagerank.hip", "gmx_pr_cold.hip")
@@ -173,6 +175,29 @@ def extras(gmx, graph26, scale):
     return out
 
 
+def dump_outputs(out_dir, engine, graph, last_diff, rank, world, coll_dev):
+    """rank[] after the last timed step at DUMP_SAMPLE vertices (seeded, the same for every run of a graph size), the
+    vertex ids of the sample and the step's diff.  For N > 1 each rank holds its own rows only (zeros elsewhere): the
+    samples are summed over the ranks."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    V = graph.V
+    vertex = np.sort(np.random.default_rng(1997).choice(V, min(V, DUMP_SAMPLE), replace=False))
+    full = engine.download()
+    sample = full[vertex]
+    del full
+    if world > 1:
+        t = torch.from_numpy(sample.astype(np.float64)).to(coll_dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        sample = t.cpu().numpy().astype(sample.dtype)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "rank_sample.npy"), sample)
+        np.save(os.path.join(out_dir, "rank_sample_vertex.npy"), vertex.astype(np.float64))
+        np.save(os.path.join(out_dir, "diff.npy"), np.array([last_diff], np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -185,9 +210,19 @@ def main():
     ap.add_argument("--chunks", type=int, default=0, help="row chunks per step for N > 1 (0: 2 when the sliced variant runs)")
     ap.add_argument("--exchange", default="auto", choices=["auto", "push", "collective"],
                     help="N > 1: peer copies over xGMI (hipIpc + copy engines) or RCCL all-gather; auto = push if it sets up")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the device copy rate, the other BASELINE configurations and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other BASELINE configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (sampled rank[], diff) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.full:
+        # the CPU baseline pins its OpenMP threads like the reference's run.sh does (scripts/run.sh:237-238,350);
+        # libgomp reads this once, when it is first loaded (torch below loads it)
+        os.environ.setdefault("GOMP_CPU_AFFINITY", "0-%d" % ((os.cpu_count() or 1) - 1))
 
     # Keep stdout clean for the ONE JSON line: libraries (RCCL prints a version banner to stdout) are
     # pointed at stderr for the whole run, the result goes to the saved descriptor at the end.
@@ -351,8 +386,10 @@ def main():
         pass
 
     kernel_name = engine.state.kernel_name()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engine, graph, last_diff, rank, world, coll_dev)
     cpu = extra = copy_gbs = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         engine.state.free()   # make room: the extras build their own plans
         copy_gbs = gmx.copy_bandwidth(1 << 30, 10)
         if not args.no_extra and args.edge_factor == 16:

@@ -1340,12 +1340,44 @@ def test_pagerank_damping_outside_unit_interval(gmx):
     g.free()
 
 
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_bench_dump_outputs_match_oracle(gmx, tmp_path, dtype):
+    """bench.py --dump-outputs: after `--warmup W --steps K` the dumped rank[] sample is the oracle's rank after W + K
+    iterations at the dumped vertex ids, and the dumped diff is that iteration's; the result line reports K steps."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    scale, warmup, steps = 21, 2, 3
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", str(scale), "--dtype", dtype,
+                        "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["roofline"]["launches"] == steps and out["ms_per_step"] > 0 and out["dtype"] == dtype
+    sample = np.load(tmp_path / "rank_sample.npy")
+    vertex = np.load(tmp_path / "rank_sample_vertex.npy")
+    diff = np.load(tmp_path / "diff.npy")
+    assert sample.dtype == (np.float32 if dtype == "f32" else np.float64) and vertex.dtype == np.float64
+    assert sample.shape == vertex.shape and 0 < len(vertex) < (1 << scale) and diff.shape == (1,)
+    g = gmx.Graph.rmat(1 << scale, 16 << scale, 1997, 0.57, 0.19, 0.19, True)     # bench.py's graph (== the oracle's generator)
+    og = po.Graph(g.V, *g.download())
+    g.free()
+    want, _, want_diff = po.pagerank(og, 1e-300, 0.85, warmup + steps)
+    err = rel_err(sample, want[vertex.astype(np.int64)])
+    assert err < (PR_RTOL_F32 if dtype == "f32" else PR_RTOL_F64), err
+    assert abs(diff[0] - want_diff) < 1e-3 * want_diff, (diff[0], want_diff)
+
+
 @pytest.mark.parametrize("nranks", [2, 3])
-def test_bench_multi_rank_rehearsal(nranks):
+def test_bench_multi_rank_rehearsal(nranks, tmp_path):
     """bench.py --gpus N as the driver launches it (torch.distributed.run, one process per rank), with the ranks sharing
     this box's one GPU (GMX_BENCH_SHARED_GPU=1: gloo + host barrier instead of RCCL; the peer pushes go through hipIpc as
     on a real node).  What it proves is this file's N > 1 code path end to end: warm-up agreement, the pipelined pushed
-    step, the replica check after the timed steps (no fallback), one JSON line from rank 0."""
+    step, the replica check after the timed steps (no fallback), one JSON line from rank 0, and --dump-outputs
+    assembling every rank's rows (a vertex's rank is never 0, so a missing slice would show)."""
     import json
     import socket
     import subprocess
@@ -1357,7 +1389,8 @@ def test_bench_multi_rank_rehearsal(nranks):
     env = dict(os.environ, GMX_BENCH_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--scale", "22",
-                        "--steps", "4", "--warmup", "2"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
+                        "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -1368,3 +1401,5 @@ def test_bench_multi_rank_rehearsal(nranks):
     assert cfg["step_form"] == "pushed, pipelined", cfg["step_form"]      # no fallback
     assert cfg["exchange_packed"] is True and cfg["exchange_bytes_per_rank_and_step"] > 0
     assert "rehearsal" in cfg
+    sample = np.load(tmp_path / "rank_sample.npy")
+    assert sample.shape == np.load(tmp_path / "rank_sample_vertex.npy").shape and np.all(sample > 0)
