@@ -1610,6 +1610,14 @@ static int bfs_run(gmx_bfs* b, gmx_node_t root) {
     return GMX_OK;
 }
 
+int gmx_bfs_reach(gmx_graph* g, int32_t root, const int32_t** dist, int64_t* edges) {
+    if (!g->bfs_cache) GMX_CHECK(gmx_bfs_create(g, 0, 1, &g->bfs_cache));
+    GMX_CHECK(bfs_run(g->bfs_cache, root));
+    *dist = g->bfs_cache->dist.p;
+    *edges = (int64_t) g->bfs_cache->edges;
+    return GMX_OK;
+}
+
 // ---- the visits of an InBFS traversal (gm_bfs_template.h:69-312: visit_fw / visit_rv, as gm_cpp_gen_bfs.cc:88-275 emits
 // them) as device functors.  A VISIT is: for every vertex v of a level, S = Sum over its UpNbrs (in-neighbours one level
 // closer, DIR = -1, through the reverse CSR) or DownNbrs (out-neighbours one level deeper, DIR = +1: the template's

@@ -337,6 +337,7 @@ void gmx_warm_modules() {
     gmx_touch_pagerank();
     gmx_touch_pr_cold();
     gmx_touch_bfs();
+    gmx_touch_scc();
 }
 
 static int check_sizes(int64_t V, int64_t E) {
@@ -744,6 +745,14 @@ extern "C" int gmx_graph_free(gmx_graph_t* g) {
         g->tc_oriented = nullptr;
         if (g->bfs_cache) gmx_bfs_free(g->bfs_cache);
         g->bfs_cache = nullptr;
+        if (gmx_graph* t = g->scc_transpose) {   // the arrays are g's
+            t->begin.take();
+            t->node_idx.take();
+            t->r_begin.take();
+            t->r_node_idx.take();
+            gmx_graph_free(t);
+            g->scc_transpose = nullptr;
+        }
     }
     delete g;
     return GMX_OK;

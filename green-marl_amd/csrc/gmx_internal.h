@@ -141,7 +141,14 @@ struct gmx_graph {
     dbuf<int32_t> bfs_hub_id;     // [bfs_hubs]; empty when every vertex is a hub (slot = id)
     int64_t bfs_hubs = 0;
     bool bfs_hint_plain = false;  // V > 2^30: the hints are plain vertex ids (no room for the flag bits)
+    // scc: the transposed view (g's four CSR arrays with the roles swapped, its own traversal object and hints) that the
+    // backward traversal runs on; it borrows the arrays and is freed with g (gmx_scc.hip)
+    gmx_graph* scc_transpose = nullptr;
 };
+
+// root's whole traversal on g's single-rank traversal object (created on first use, as gmx_hop_dist does): *dist = its
+// device dist[] (INT_MAX = unreached, valid until the next traversal on g), *edges = edge slots inspected (gmx_bfs.hip)
+int gmx_bfs_reach(gmx_graph* g, int32_t root, const int32_t** dist, int64_t* edges);
 
 // ---- graph construction helpers (gmx_graph.hip) ----
 // keys are (row << 32 | col).  Sorts keys in place (double buffer), then writes
@@ -225,6 +232,7 @@ struct gmx_tick {
 void gmx_touch_pagerank();
 void gmx_touch_pr_cold();
 void gmx_touch_bfs();
+void gmx_touch_scc();
 void gmx_warm_modules();   // once per process: load every translation unit's code object (see gmx_touch_*)
 
 static inline int gmx_bits_for(int64_t v) {  // bits needed to represent values in [0, v)

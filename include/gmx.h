@@ -188,6 +188,15 @@ int gmx_sssp(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host, int32_t* 
 int gmx_avg_teen_cnt(gmx_graph_t* g, const int32_t* age_host, int32_t K, int32_t* teen_cnt_host, float* avg, gmx_stats_t* stats);
 int gmx_conduct(gmx_graph_t* g, const int32_t* member_host, int32_t num, float* result, gmx_stats_t* stats);
 
+/* kosaraju(G, mem) (apps/src/kosaraju.gm; driver apps/output_cpp/src/kosaraju_main.cc): the strongly connected
+ * components.  *num_comps = their number and comp_host[V] = the component of every vertex -- the same partition and count
+ * as the reference, but numbered CANONICALLY: ids run densely over 0 .. count-1 in increasing order of each component's
+ * smallest vertex id (the reference numbers them in its sequential DFS finish order).  Deterministic from run to run.
+ * Needs the reverse CSR (GMX_ERR_STATE after an upload with GMX_GRAPH_NO_REVERSE).  stats: iterations = outer
+ * trim / FW-BW / colouring rounds, vertices_reached = size of the largest SCC, edges_examined = edge slots inspected,
+ * kernel_ms = device time, d2h_ms = download of comp. */
+int gmx_scc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, gmx_stats_t* stats);
+
 /* triangle_counting(G) with the emitted multiplicity rule. */
 int gmx_triangle_counting(gmx_graph_t* g, int64_t* count, gmx_stats_t* stats);
 /* Multi-GPU form (replicated CSR, final all-reduce of int64): the count contributed by part
