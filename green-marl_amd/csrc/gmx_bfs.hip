@@ -371,7 +371,7 @@ bfs_topdown_sparse_kernel(const int32_t* __restrict__ begin, const int32_t* __re
 }
 
 // The level out of the ROOT (every traversal's first): one row, nobody else visited.  Its distinct entries (the rows are
-// sorted: a repeated edge sits next to its copy) other than the root itself all get level + 1 -- no look at dist[], no
+// sorted -- gmx_graph::rows_sorted, checked at the launch: a repeated edge sits next to its copy) other than the root itself all get level + 1 -- no look at dist[], no
 // atomicMin: the general kernel spent 75-84 us on the 0.98 M out-edges of RMAT-26's vertex 0, four dependent random accesses
 // per edge.  With bm32 the frontier bitmap of the next level is written here too (a large row is followed by a bottom-up
 // level, which otherwise starts with a pass over the new queue: 35 us).
@@ -1169,7 +1169,9 @@ extern "C" int gmx_bfs_step_begin(gmx_bfs_t* b, int* needs_exchange) {
             b->explored += m_f;
         }
         b->frontier_bm_valid = false;
-        if (b->level == 0 && b->cur_count == 1 && b->root >= 0 && !have_off) {   // the level out of the root
+        // the level out of the root, on sorted rows only (its kernel drops a repeat by comparing with the slot before; a
+        // repeat elsewhere in an unsorted row would enter the queue once per copy): other rows take the general levels below
+        if (b->level == 0 && b->cur_count == 1 && b->root >= 0 && !have_off && g->rows_sorted) {
             // (the counters are clear: bfs_init_kernel)  A row this large is followed by a bottom-up level: write its bitmap too
             // (liberal: a wrong guess costs a memset of the bitmap later, a missed one a pass over the queue now)
             const bool with_bm = g->has_reverse && b->bm_clean[b->fr] && m_f >= 64 && m_f >= V / 1024;

@@ -245,13 +245,53 @@ __global__ void iota_i32_kernel(int32_t* __restrict__ p, int64_t n) {
     for (; i < n; i += stride) p[i] = (int32_t) i;
 }
 
-// flag[0] |= 1 if some row of the CSR is not ascending
-__global__ void rows_unsorted_kernel(const uint64_t* __restrict__ keys, int64_t E, int* __restrict__ flag) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x + 1;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    bool bad = false;
-    for (; i < E; i += stride) bad |= keys[i] < keys[i - 1];   // keys are (row << 32 | col) in slot order
-    if (bad) atomicOr(flag, 1);
+// Validation of an uploaded CSR, one pass over its device copy: res[0] = a row r with begin[r] > begin[r + 1], res[1] =
+// a slot whose value lies outside [0, V), res[2] = a slot smaller than the slot before it in its row (~0: none; the
+// smallest such index).  The host has checked begin[0] == 0 and begin[V] == E, which keeps the row walk inside begin[]
+// whatever the rows in between hold.
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long y = __shfl_xor(x, o, 64);
+        x = y < x ? y : x;
+    }
+    return x;
+}
+
+__global__ void csr_check_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ idx, int64_t V, int64_t E,
+                                 unsigned long long* __restrict__ res) {
+    const int64_t t = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x, nchunks = (E + KFC_CHUNK - 1) / KFC_CHUNK;
+    unsigned long long bad_b = ~0ULL, bad_v = ~0ULL, bad_s = ~0ULL;
+    for (int64_t r = t; r < V; r += stride)
+        if (begin[r] > begin[r + 1] && (unsigned long long) r < bad_b) bad_b = (unsigned long long) r;
+    for (int64_t c = t; c < nchunks; c += stride) {   // KFC_CHUNK consecutive slots: as keys_from_csr_kernel walks them
+        const int64_t e0 = c * KFC_CHUNK, e1 = e0 + KFC_CHUNK < E ? e0 + KFC_CHUNK : E;
+        int64_t lo = 0, hi = V;   // largest r with begin[r] <= e0
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t) begin[mid] <= e0) lo = mid; else hi = mid;
+        }
+        int64_t row = lo, first = begin[row], next = begin[row + 1];
+        for (int64_t e = e0; e < e1; e++) {
+            while (e >= next) {   // (stops at row V - 1 at the latest: begin[V] = E > e)
+                row++;
+                first = next;
+                next = begin[row + 1];
+            }
+            const int32_t v = idx[e];
+            if ((v < 0 || (int64_t) v >= V) && (unsigned long long) e < bad_v) bad_v = (unsigned long long) e;
+            if (e > 0 && e > first && idx[e - 1] > v && (unsigned long long) e < bad_s) bad_s = (unsigned long long) e;
+        }
+    }
+    bad_b = wave_min_u64(bad_b);
+    bad_v = wave_min_u64(bad_v);
+    bad_s = wave_min_u64(bad_s);
+    if ((threadIdx.x & 63) == 0) {
+        if (bad_b != ~0ULL) atomicMin(&res[0], bad_b);
+        if (bad_v != ~0ULL) atomicMin(&res[1], bad_v);
+        if (bad_s != ~0ULL) atomicMin(&res[2], bad_s);
+    }
 }
 
 int gmx_csr_from_keys(uint64_t* keys, uint64_t* keys_alt, int64_t V, int64_t E,
@@ -289,26 +329,36 @@ int gmx_csr_from_keys(uint64_t* keys, uint64_t* keys_alt, int64_t V, int64_t E,
     return GMX_OK;
 }
 
+// Checks the device copy (begin, idx) of an uploaded CSR (csr_check_kernel); h_begin / h_idx are the caller's arrays,
+// read for the message only.  *sorted = every row non-decreasing.  GMX_ERR_ARG names what failed.
+static int check_uploaded_csr(const int32_t* begin, const int32_t* idx, const int32_t* h_begin, const int32_t* h_idx,
+                              int64_t V, int64_t E, const char* what, bool* sorted) {
+    dbuf<unsigned long long> res;
+    GMX_CHECK(res.alloc(3));
+    GMX_HIP(hipMemsetAsync(res.p, 0xff, 3 * sizeof(unsigned long long), 0));
+    const int64_t items = V > (E + KFC_CHUNK - 1) / KFC_CHUNK ? V : (E + KFC_CHUNK - 1) / KFC_CHUNK;
+    hipLaunchKernelGGL(csr_check_kernel, dim3(grid_for(items)), dim3(256), 0, 0, begin, idx, V, E, res.p);
+    GMX_HIP(hipGetLastError());
+    unsigned long long h[3];
+    GMX_HIP(hipMemcpy(h, res.p, sizeof(h), hipMemcpyDeviceToHost));
+    GMX_REQUIRE(h[0] == ~0ULL, "%s: begin decreases at row %llu (%d -> %d)", what, h[0], h_begin[h[0]], h_begin[h[0] + 1]);
+    GMX_REQUIRE(h[1] == ~0ULL, "%s: node_idx[%llu] = %d lies outside [0, V = %lld)", what, h[1], h_idx[h[1]], (long long) V);
+    *sorted = h[2] == ~0ULL;
+    return GMX_OK;
+}
+
 // Build forward (and reverse) CSR of g from device keys (row<<32|col), consuming them.
-// sorted_csr (optional): the uploaded CSR the keys were made from; when its rows turn out to be in order already it
-// becomes the forward CSR as it is (no sort, identity e_idx2idx)
-static int build_from_forward_keys(gmx_graph* g, wbuf<uint64_t>& keys, wbuf<uint64_t>& alt, bool want_reverse, bool keep_order = false,
-                                   dbuf<int32_t>* up_begin = nullptr, dbuf<int32_t>* up_idx = nullptr) {
+// up_begin / up_idx (optional): the uploaded CSR the keys were made from, and up_sorted whether its rows are in order (the
+// upload's validation pass found it).  In order, it becomes the forward CSR as it is (no sort, identity e_idx2idx);
+// otherwise the sort records where every sorted slot came from (e_idx2idx), with or without GMX_GRAPH_SORT_ROWS.
+static int build_from_forward_keys(gmx_graph* g, wbuf<uint64_t>& keys, wbuf<uint64_t>& alt, bool want_reverse,
+                                   dbuf<int32_t>* up_begin = nullptr, dbuf<int32_t>* up_idx = nullptr, bool up_sorted = false) {
     hipStream_t s = 0;
     int32_t* slots = nullptr;
-    bool in_order = false;
-    if ((keep_order || (up_begin && up_idx)) && g->E > 1) {   // rows out of order + keep_order: remember where every sorted slot came from (e_idx2idx)
-        dbuf<int> flag;
-        GMX_CHECK(flag.alloc(1));
-        GMX_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), s));
-        hipLaunchKernelGGL(rows_unsorted_kernel, dim3(grid_for(g->E)), dim3(256), 0, s, (const uint64_t*) keys.p, g->E, flag.p);
-        int h = 0;
-        GMX_HIP(hipMemcpy(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost));
-        if (h && keep_order) {
-            GMX_CHECK(g->e_idx2idx.alloc((size_t) g->E));
-            slots = g->e_idx2idx.p;
-        }
-        in_order = !h && up_begin && up_idx;
+    const bool in_order = up_begin && up_idx && up_sorted;
+    if (up_begin && up_idx && !up_sorted && g->E > 1) {
+        GMX_CHECK(g->e_idx2idx.alloc((size_t) g->E));
+        slots = g->e_idx2idx.p;
     }
     if (in_order) {   // (what a file written after a semi-sort looks like)
         g->begin.p = up_begin->take();
@@ -358,14 +408,20 @@ extern "C" int gmx_graph_upload(const gmx_edge_t* begin, const gmx_node_t* node_
     GMX_REQUIRE(begin && (node_idx || E == 0), "begin/node_idx is NULL");
     GMX_REQUIRE(begin[0] == 0 && (int64_t) begin[V] == E, "begin[0]=%d begin[V]=%d do not match E=%lld",
                 begin[0], begin[V], (long long) E);
+    const bool want_rev = !(flags & GMX_GRAPH_NO_REVERSE), keys_path = (flags & GMX_GRAPH_SORT_ROWS) || (want_rev && !r_begin);
+    if (want_rev && !keys_path) {
+        GMX_REQUIRE(r_node_idx || E == 0, "r_node_idx is NULL");
+        GMX_REQUIRE(r_begin[0] == 0 && (int64_t) r_begin[V] == E, "r_begin[0]=%d r_begin[V]=%d do not match E=%lld",
+                    r_begin[0], r_begin[V], (long long) E);
+    }
     gmx_graph* g = new gmx_graph();
     g->V = V;
     g->E = E;
     (void) hipGetDevice(&g->device);
+    gmx_tick tick("upload");
     int st = GMX_OK;
     do {
-        bool want_rev = !(flags & GMX_GRAPH_NO_REVERSE);
-        if ((flags & GMX_GRAPH_SORT_ROWS) || (want_rev && !r_begin)) {
+        if (keys_path) {
             // go through keys: sorts rows and/or builds the reverse CSR on the device
             dbuf<int32_t> tb, ti;
             wbuf<uint64_t> keys, alt;
@@ -377,9 +433,13 @@ extern "C" int gmx_graph_upload(const gmx_edge_t* begin, const gmx_node_t* node_
                 st = GMX_ERR_HIP;
                 break;
             }
+            tick.mark("H2D copy");
+            bool sorted = true;
+            if ((st = check_uploaded_csr(tb.p, ti.p, begin, node_idx, V, E, "CSR", &sorted))) break;   // (before any key is built)
+            tick.mark("validation");
             if ((st = gmx_keys_from_csr(tb.p, ti.p, V, E, false, nullptr, keys.p, 0))) break;
-            if ((st = build_from_forward_keys(g, keys, alt, want_rev, (flags & GMX_GRAPH_SORT_ROWS) != 0, &tb, &ti))) break;
-        } else {
+            if ((st = build_from_forward_keys(g, keys, alt, want_rev, &tb, &ti, sorted))) break;
+        } else {   // the caller's arrays verbatim
             if ((st = g->begin.alloc((size_t) V + 1)) || (st = g->node_idx.alloc((size_t) E))) break;
             if (hipMemcpy(g->begin.p, begin, sizeof(int32_t) * ((size_t) V + 1), hipMemcpyHostToDevice) != hipSuccess ||
                 (E && hipMemcpy(g->node_idx.p, node_idx, sizeof(int32_t) * (size_t) E, hipMemcpyHostToDevice) != hipSuccess)) {
@@ -388,7 +448,6 @@ extern "C" int gmx_graph_upload(const gmx_edge_t* begin, const gmx_node_t* node_
                 break;
             }
             if (want_rev) {
-                if (!(r_node_idx || E == 0)) { gmx_set_error("r_node_idx is NULL"); st = GMX_ERR_ARG; break; }
                 if ((st = g->r_begin.alloc((size_t) V + 1)) || (st = g->r_node_idx.alloc((size_t) E))) break;
                 if (hipMemcpy(g->r_begin.p, r_begin, sizeof(int32_t) * ((size_t) V + 1), hipMemcpyHostToDevice) != hipSuccess ||
                     (E && hipMemcpy(g->r_node_idx.p, r_node_idx, sizeof(int32_t) * (size_t) E, hipMemcpyHostToDevice) != hipSuccess)) {
@@ -398,6 +457,10 @@ extern "C" int gmx_graph_upload(const gmx_edge_t* begin, const gmx_node_t* node_
                 }
                 g->has_reverse = true;
             }
+            tick.mark("H2D copy");
+            if ((st = check_uploaded_csr(g->begin.p, g->node_idx.p, begin, node_idx, V, E, "CSR", &g->rows_sorted))) break;
+            if (want_rev && (st = check_uploaded_csr(g->r_begin.p, g->r_node_idx.p, r_begin, r_node_idx, V, E, "reverse CSR", &g->r_rows_sorted))) break;
+            tick.mark("validation");
         }
     } while (0);
     if (st != GMX_OK) { delete g; return st; }

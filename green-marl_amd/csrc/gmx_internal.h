@@ -115,6 +115,9 @@ struct gmx_graph {
     // gm_graph's e_idx2idx (gm_graph.h:141, do_semi_sort gm_graph.cc:468-503): slot of the uploaded (unsorted) forward
     // CSR that every slot of the sorted rows came from.  Empty: the upload was already in order (identity).
     dbuf<int32_t> e_idx2idx;
+    // every row of node_idx (r_node_idx) non-decreasing.  Graphs built on the device are sorted by construction; an upload
+    // that keeps the caller's arrays verbatim records what its validation pass found (gmx.h: the sorted-row contract)
+    bool rows_sorted = true, r_rows_sorted = true;
     int device = 0;
     // PageRank plans built by the whole-kernel entries (fp32, fp64), kept for the next call on the same
     // graph: the plan is graph preprocessing, like the reverse CSR.  Freed with the graph.

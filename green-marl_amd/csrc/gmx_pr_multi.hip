@@ -142,6 +142,8 @@ static int clone_graph(const gmx_graph* g, int device, gmx_graph** out) {
     h->V = g->V;
     h->E = g->E;
     h->has_reverse = g->has_reverse;
+    h->rows_sorted = g->rows_sorted;
+    h->r_rows_sorted = g->r_rows_sorted;
     h->device = device;
     int st = GMX_OK;
     GMX_HIP(hipSetDevice(device));

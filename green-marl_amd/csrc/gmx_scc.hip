@@ -544,6 +544,8 @@ static gmx_graph* scc_transposed(gmx_graph* g) {
         t->V = g->V;
         t->E = g->E;
         t->has_reverse = true;
+        t->rows_sorted = g->r_rows_sorted;
+        t->r_rows_sorted = g->rows_sorted;
         t->device = g->device;
         t->begin.p = g->r_begin.p;
         t->begin.n = g->r_begin.n;

@@ -394,7 +394,7 @@ __global__ void tc_invert_kernel(const int32_t* __restrict__ order, int64_t V, i
 static int tc_counting_graph(gmx_graph* g, gmx_graph** out, bool* oriented) {
     *out = g;
     *oriented = false;
-    if (!g->has_reverse || g->E == 0 || getenv("GMX_TC_NO_ORIENT")) return GMX_OK;
+    if (!g->has_reverse || !g->r_rows_sorted || g->E == 0 || getenv("GMX_TC_NO_ORIENT")) return GMX_OK;
     if (g->tc_sym_state < 0) {
         hipStream_t s = 0;
         dbuf<uint64_t> keys, alt;
@@ -488,6 +488,15 @@ static int tc_counting_graph(gmx_graph* g, gmx_graph** out, bool* oriented) {
 
 static int tc_count_part(gmx_graph_t* g, int part, int nparts, bool common_nbr_form, int64_t* count, gmx_stats_t* stats);
 
+// The kernels below binary-search rows and find repeats next to each other: they need the forward rows sorted (gmx.h).  A
+// reverse CSR with unsorted rows is not searched (triangle counting takes the forward-only form instead).
+static int tc_require_sorted_rows(const gmx_graph* g, const char* who) {
+    if (g->rows_sorted) return GMX_OK;
+    gmx_set_error("%s needs sorted rows: this graph was uploaded verbatim with rows out of order (upload it with "
+                  "GMX_GRAPH_SORT_ROWS)", who);
+    return GMX_ERR_STATE;
+}
+
 extern "C" int gmx_triangle_counting(gmx_graph_t* g, int64_t* count, gmx_stats_t* stats) {
     return tc_count_part(g, 0, 1, false, count, stats);
 }
@@ -510,6 +519,7 @@ static int tc_count_part(gmx_graph_t* g, int part, int nparts, bool common_nbr_f
     if (stats) memset(stats, 0, sizeof(*stats));
     *count = 0;
     if (g->E == 0) return GMX_OK;
+    GMX_CHECK(tc_require_sorted_rows(g, "triangle counting"));
     // graph preprocessing (cached on the graph like the reverse CSR; outside the timed region)
     gmx_graph* cg = nullptr;
     bool oriented = false;
@@ -520,7 +530,7 @@ static int tc_count_part(gmx_graph_t* g, int part, int nparts, bool common_nbr_f
         rbeg = g->begin.p;
         ridx = g->node_idx.p;
     }
-    const bool have_rows = g->has_reverse || oriented || common_nbr_form;
+    const bool have_rows = (g->has_reverse && g->r_rows_sorted) || oriented || common_nbr_form;   // (else: the forward-only form)
     g = cg;
     // local slot indices of this part: whole deal blocks (slots past E are skipped in the kernels)
     const int64_t deal = (int64_t) 1 << TC_DEAL_SHIFT;
@@ -624,6 +634,7 @@ common_nbr_list_kernel(const int32_t* __restrict__ begin, const int32_t* __restr
 extern "C" int gmx_common_nbr_counts(gmx_graph_t* g, const gmx_node_t* src, const gmx_node_t* dst, int64_t npairs, int64_t* counts) {
     GMX_REQUIRE(g && counts && ((src && dst) || npairs == 0) && npairs >= 0, "bad argument");
     if (npairs == 0) return GMX_OK;
+    GMX_CHECK(tc_require_sorted_rows(g, "gmx_common_nbr_counts"));
     for (int64_t i = 0; i < npairs; i++)
         GMX_REQUIRE(src[i] >= 0 && src[i] < g->V && dst[i] >= 0 && dst[i] < g->V, "pair %lld: vertex out of range", (long long) i);
     dbuf<int32_t> ds, dd;
@@ -645,6 +656,7 @@ extern "C" int gmx_common_nbr_counts(gmx_graph_t* g, const gmx_node_t* src, cons
 extern "C" int gmx_common_nbrs(gmx_graph_t* g, gmx_node_t s, gmx_node_t d, gmx_node_t* out, int64_t cap, int64_t* n) {
     GMX_REQUIRE(g && n && (out || cap == 0) && cap >= 0, "bad argument");
     GMX_REQUIRE(s >= 0 && s < g->V && d >= 0 && d < g->V, "vertex out of range");
+    GMX_CHECK(tc_require_sorted_rows(g, "gmx_common_nbrs"));
     dbuf<int32_t> dout;
     dbuf<int64_t> dn;
     GMX_CHECK(dout.alloc((size_t) (cap ? cap : 1)));

@@ -74,11 +74,33 @@ int gmx_workspace_release(void);
 
 #define GMX_GRAPH_SORT_ROWS    0x1u  /* rows of node_idx are not sorted yet: do_semi_sort on device   */
 #define GMX_GRAPH_NO_REVERSE   0x2u  /* do not keep a reverse CSR (BFS top-down only / TC binary search) */
+/* Without GMX_GRAPH_SORT_ROWS an upload that builds the reverse CSR on the device (r_begin NULL, no
+ * GMX_GRAPH_NO_REVERSE) sorts the forward rows on the way when they are out of order, and then behaves exactly as if
+ * GMX_GRAPH_SORT_ROWS had been passed: sorted rows on the device and an e_idx2idx map (gmx_graph_edge_order). */
 
 /* Upload a host CSR.  begin[V+1], node_idx[E] = gm_graph::begin / node_idx.
  * r_begin / r_node_idx = gm_graph::r_begin / r_node_idx, or NULL: the reverse
  * CSR is then built on the device (gm_graph::make_reverse_edges, gm_graph.cc:205-304,
- * followed by do_semi_sort_reverse, :461-466). */
+ * followed by do_semi_sort_reverse, :461-466).
+ *
+ * Validation (GMX_ERR_ARG, the message says what failed): begin[0] = 0, begin[V] = E, begin never decreases, and every
+ * node_idx value lies in [0, V).  A reverse CSR the upload keeps (given, without GMX_GRAPH_SORT_ROWS and without
+ * GMX_GRAPH_NO_REVERSE) is checked the same way (r_begin[0] = 0, r_begin[V] = E, ...).  These checks run on the device
+ * copies, before anything is built from them.  That a given reverse CSR is the transpose of the forward one is NOT
+ * checked: it is the caller's responsibility, and every entry that reads the reverse CSR trusts it.
+ *
+ * Sorted rows ("semi-sorted": every row non-decreasing).  Graphs built on the device (gmx_graph_from_edges,
+ * gmx_graph_create_rmat, gmx_graph_symmetrize) and uploads through GMX_GRAPH_SORT_ROWS or a device-built reverse CSR
+ * have sorted rows.  The other uploads keep the caller's arrays verbatim (with GMX_GRAPH_NO_REVERSE: the forward ones),
+ * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
+ * CSR's rows are sorted.  On such a graph:
+ *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
+ *     gmx_scc and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len is indexed by the stored slots);
+ *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs and
+ *     gmx_common_nbr_counts binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
+ *     gm_common_neighbor_iter.h): GMX_ERR_STATE when the forward rows are not sorted.  With sorted forward rows and an
+ *     unsorted reverse CSR, triangle counting takes the forward-only form of a GMX_GRAPH_NO_REVERSE graph. */
 int gmx_graph_upload(const gmx_edge_t* begin, const gmx_node_t* node_idx,
                      const gmx_edge_t* r_begin, const gmx_node_t* r_node_idx,
                      int64_t V, int64_t E, uint32_t flags, gmx_graph_t** out);
@@ -108,9 +130,9 @@ int gmx_graph_reverse_edge_map_e64(const gmx_graph_t* g, int64_t* e_rev2idx);
 int gmx_graph_free(gmx_graph_t* g);
 int64_t gmx_graph_num_nodes(const gmx_graph_t* g);
 int64_t gmx_graph_num_edges(const gmx_graph_t* g);
-/* gm_graph's e_idx2idx[E] (gm_graph.h:141, do_semi_sort gm_graph.cc:468-503) after an upload with
- * GMX_GRAPH_SORT_ROWS: for every slot of the sorted rows, the slot of the uploaded CSR it came from (equal
- * destinations keep their order).  *is_identity = 1 when the upload was already in order; e_idx2idx is then not
+/* gm_graph's e_idx2idx[E] (gm_graph.h:141, do_semi_sort gm_graph.cc:468-503) after an upload that sorted the rows
+ * (GMX_GRAPH_SORT_ROWS, or a device-built reverse CSR): for every slot of the sorted rows, the slot of the uploaded CSR
+ * it came from (equal destinations keep their order).  *is_identity = 1 when the upload was already in order; e_idx2idx is then not
  * written.  Edge properties passed later (gmx_sssp's len) are indexed by the UPLOADED slots. */
 int gmx_graph_edge_order(const gmx_graph_t* g, gmx_edge_t* e_idx2idx, int* is_identity);
 /* gm_graph's e_rev2idx[E] (gm_graph.h:141-142): forward slot mirrored by each slot of the reverse CSR. */

@@ -803,8 +803,15 @@ def test_peer_push_exchange_between_processes(gmx, world, chunks, elem, binned):
 
 def _bfs_ranks_in_one_process(gmx, og, root, nranks):
     """N rank states of the partitioned hop_dist side by side; device copies stand in for the all-gather."""
-    import torch
     g = gmx.Graph.upload(og.begin, og.node_idx, og.r_begin, og.r_node_idx)
+    out = _bfs_ranks_on_graph(gmx, g, root, nranks)
+    g.free()
+    return out
+
+
+def _bfs_ranks_on_graph(gmx, g, root, nranks):
+    """_bfs_ranks_in_one_process on a graph already on the device."""
+    import torch
     states = [gmx.BfsState(g, r, nranks) for r in range(nranks)]
     for s in states:
         s.start(root)
@@ -831,7 +838,6 @@ def _bfs_ranks_in_one_process(gmx, og, root, nranks):
     outs = [s.download()[0] for s in states]
     for s in states:
         s.free()
-    g.free()
     return outs, levels, exchanges
 
 

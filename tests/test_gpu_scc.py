@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLD, ROOT
-from test_scc_host import canonical, csr_of, kosaraju_check, scipy_scc
+from test_scc_host import canonical, kosaraju_check, scipy_scc
+from test_upload_forms_host import unsorted_multigraph as _unsorted_multigraph
 
 pytestmark = pytest.mark.gpu
 PKG = os.path.join(ROOT, "green-marl_amd")
@@ -143,22 +144,6 @@ def test_rmat_against_scipy(gmx, scale):
     pytest.importorskip("scipy")
     g = gmx.Graph.rmat(1 << scale, 16 << scale, 1997, 0.57, 0.19, 0.19, scale % 4 == 2)
     check(g)
-
-
-def _unsorted_multigraph(V, hub_edges, seed):
-    """A random strongly connected core (cycle + chords), a DAG tail, and a hub (vertex 5) whose out-row holds
-    hub_edges > V entries with repeats, every row shuffled; forward and reverse CSR as uploaded verbatim."""
-    rng = np.random.default_rng(seed)
-    core = V // 2
-    c = np.arange(core)
-    s = [c, rng.integers(0, core, 2 * core), np.full(hub_edges, 5), rng.integers(0, V, V)]
-    d = [(c + 1) % core, rng.integers(0, core, 2 * core), rng.integers(0, V, hub_edges), None]
-    d[3] = np.minimum(V - 1, s[3] + 1 + rng.integers(0, 4, V))   # forward-only edges
-    s, d = np.concatenate(s), np.concatenate(d)
-    sh = rng.permutation(len(s))
-    s, d = s[sh], d[sh]
-    begin, idx, rb, ri = csr_of(V, s, d)   # rows keep the shuffled order
-    return begin, idx, rb, ri
 
 
 @pytest.mark.parametrize("V,hub_edges", [(64, 200), (150000, 400000)])
