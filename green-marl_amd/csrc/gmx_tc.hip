@@ -668,3 +668,215 @@ extern "C" int gmx_common_nbrs(gmx_graph_t* g, gmx_node_t s, gmx_node_t d, gmx_n
     if (m > 0) GMX_HIP(hipMemcpy(out, dout.p, sizeof(int32_t) * (size_t) m, hipMemcpyDeviceToHost));
     return GMX_OK;
 }
+
+// ------------------------------------------------------------------ adamicAdar: one sum per edge over the iterator
+// adamicAdar(G, aa) (apps/src/adamicAdar.gm; driver apps/output_cpp/src/adamicAdar_main.cc; the only application whose
+// emitted C++ uses gm_common_neighbor_iter): for every forward slot e = (from -> to)
+//     aa[e] = sum over the slots j of row(from), with multiplicity, whose value n occurs in row(to), of 1 / log(outdeg n).
+// Shaped like tc_oriented_kernel.  A work item is (vertex v, group of 64 of its slots); waves claim items from a counter,
+// stage row(v) in their LDS slice (once for all the groups of v inside a claim) and take the group's slots one per lane.
+// A slot whose shorter side is short is walked by its lane alone, the others by the whole wave one after the other: the
+// lanes stride over the shorter of row(from), row(to) and binary-search the longer; walking row(to) takes each distinct
+// value times its multiplicity in row(from), as tc_intersect does.  The lanes' partial sums are added in a fixed
+// butterfly, so a slot's value does not depend on which wave computed it or when: bit-identical from run to run, no
+// floating-point atomic anywhere.  Repeated slots (from, to) lie next to each other in the sorted row: the first one of a
+// group computes, the others copy.  Rows longer than the staged capacity are searched in memory by the same code
+// (GMX_AA_CAP=<entries> lowers the capacity: the tests send small graphs down that path).  Every slot's value is stored
+// once, by the lane that owns the slot, at the slot of the uploaded CSR it belongs to (e_idx2idx).
+// IEEE double throughout: 1 / log(1) = +inf, 1 / log(0) = -0.0, an empty sum is +0.0, and no term is -inf or NaN.
+#define AA_WAVES 4
+#define AA_CAP 1024     // row entries staged per wave (4 KiB; 16 KiB of LDS per workgroup: 8 workgroups, 32 waves per CU)
+#define AA_CLAIM 8      // work items per dequeue
+#define AA_ALONE 4      // a lane walks a shorter side of up to this many entries by itself (GMX_AA_ALONE)
+
+// w[v] = 1 / log(outdeg v) and the number of 64-slot groups of row v
+__global__ void aa_weight_kernel(const int32_t* __restrict__ begin, int64_t V, double* __restrict__ w, int64_t* __restrict__ groups) {
+    int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (; v < V; v += stride) {
+        const int32_t d = begin[v + 1] - begin[v];
+        w[v] = 1.0 / log((double) d);
+        groups[v] = (d + 63) >> 6;
+    }
+}
+
+// row(from) = R[0, da): the wave's LDS slice or the row in memory
+template <bool LDS>
+__device__ __forceinline__ void aa_walk_from(const int32_t* R, int32_t da, const int32_t* __restrict__ node_idx, int32_t tb, int32_t te,
+                                             const double* __restrict__ w, int first, int step, double& sum, unsigned long long& k) {
+    for (int32_t p = first; p < da; p += step) {
+        const int32_t n = R[p];
+        if (tc_contains(node_idx, tb, te, n)) {
+            sum += w[n];
+            k++;
+        }
+    }
+}
+
+template <bool LDS>
+__device__ __forceinline__ void aa_walk_to(const int32_t* R, int32_t da, const int32_t* __restrict__ node_idx, int32_t tb, int32_t te,
+                                           const double* __restrict__ w, int first, int step, double& sum, unsigned long long& k) {
+    for (int32_t p = tb + first; p < te; p += step) {
+        const int32_t x = node_idx[p];
+        if (p > tb && node_idx[p - 1] == x) continue;            // every distinct value of row(to) once
+        const int32_t lo = LDS ? tco_lds_lower_bound(R, 0, da, x) : tc_lower_bound(R, 0, da, x);
+        if (lo >= da || R[lo] != x) continue;
+        const int32_t hi = LDS ? tco_lds_lower_bound(R, lo + 1, da, x + 1) : tc_lower_bound(R, lo + 1, da, x + 1);
+        sum += (double) (hi - lo) * w[x];                          // ... times its multiplicity in row(from)
+        k += (unsigned long long) (hi - lo);
+    }
+}
+
+__global__ void __launch_bounds__(AA_WAVES * 64)
+aa_rows_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ node_idx, const double* __restrict__ w,
+               const int64_t* __restrict__ grp_off, int64_t V, int cap, int alone_max, const int32_t* __restrict__ slot_of /* or NULL */,
+               unsigned long long* __restrict__ next_claim, unsigned long long* __restrict__ hits, double* __restrict__ aa) {
+    __shared__ int32_t s_row[AA_WAVES][AA_CAP];
+    const int lane = threadIdx.x & 63;
+    int32_t* A = s_row[threadIdx.x >> 6];
+    const int64_t G = grp_off[V];
+    unsigned long long nhit = 0;
+    for (;;) {
+        unsigned long long b = 0;
+        if (lane == 0) b = atomicAdd(next_claim, (unsigned long long) AA_CLAIM);
+        b = __shfl(b, 0, 64);
+        if ((int64_t) b >= G) break;
+        int64_t v = -1, staged = -1;
+        for (int64_t item = (int64_t) b; item < (int64_t) b + AA_CLAIM && item < G; item++) {
+            if (v < 0 || grp_off[v + 1] <= item) {   // vertex of the item: last v with grp_off[v] <= item
+                int64_t lo = 0, hi = V;
+                while (hi - lo > 1) {
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (grp_off[mid] <= item) lo = mid; else hi = mid;
+                }
+                v = lo;
+            }
+            const int32_t rb = begin[v], da = begin[v + 1] - rb;
+            const int32_t* Rg = node_idx + rb;
+            const bool in_lds = da <= cap;
+            if (in_lds && staged != v) {
+                __builtin_amdgcn_wave_barrier();            // all lanes are done with the row staged before
+                for (int32_t k = lane; k < da; k += 64) A[k] = Rg[k];
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_s_waitcnt(0xc07f);         // the wave's own LDS writes are visible to all its lanes
+                __builtin_amdgcn_wave_barrier();
+                staged = v;
+            }
+            // one slot per lane
+            const int32_t i = (int32_t) (item - grp_off[v]) * 64 + lane;
+            const bool act = i < da;
+            const int32_t to = act ? (in_lds ? A[i] : Rg[i]) : -1;
+            const int32_t before = __shfl_up(to, 1, 64);
+            const bool lead = act && (lane == 0 || before != to);   // the first of the repeated slots (from, to) computes
+            int32_t tb = 0, te = 0;
+            if (lead) {
+                tb = begin[to];
+                te = begin[to + 1];
+            }
+            const int32_t db = te - tb;
+            const int32_t shorter = da <= db ? da : db;              // walk row(from) when it is not the longer one
+            double sum = 0.0;
+            unsigned long long k = 0;
+            if (lead && shorter > 0 && shorter <= alone_max) {
+                if (da <= db) {
+                    if (in_lds) aa_walk_from<true>(A, da, node_idx, tb, te, w, 0, 1, sum, k);
+                    else aa_walk_from<false>(Rg, da, node_idx, tb, te, w, 0, 1, sum, k);
+                } else {
+                    if (in_lds) aa_walk_to<true>(A, da, node_idx, tb, te, w, 0, 1, sum, k);
+                    else aa_walk_to<false>(Rg, da, node_idx, tb, te, w, 0, 1, sum, k);
+                }
+            }
+            unsigned long long m = __ballot(lead && shorter > alone_max);
+            while (m) {
+                const int src = __ffsll((long long) m) - 1;
+                m &= m - 1;
+                const int32_t stb = __shfl(tb, src, 64), ste = __shfl(te, src, 64);
+                double part = 0.0;
+                unsigned long long pk = 0;
+                if (da <= ste - stb) {
+                    if (in_lds) aa_walk_from<true>(A, da, node_idx, stb, ste, w, lane, 64, part, pk);
+                    else aa_walk_from<false>(Rg, da, node_idx, stb, ste, w, lane, 64, part, pk);
+                } else {
+                    if (in_lds) aa_walk_to<true>(A, da, node_idx, stb, ste, w, lane, 64, part, pk);
+                    else aa_walk_to<false>(Rg, da, node_idx, stb, ste, w, lane, 64, part, pk);
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {             // butterfly: every lane ends with the same sum
+                    part += __shfl_xor(part, off, 64);
+                    pk += __shfl_xor(pk, off, 64);
+                }
+                if (lane == src) {
+                    sum = part;
+                    k = pk;
+                }
+            }
+            // the repeats take the value of the first of their run
+            const unsigned long long leads = __ballot(lead) & (~0ull >> (63 - lane));
+            const int from_lane = leads ? 63 - __builtin_clzll(leads) : lane;
+            sum = __shfl(sum, from_lane, 64);
+            k = __shfl(k, from_lane, 64);
+            if (act) {
+                const int64_t e = (int64_t) rb + i;
+                aa[slot_of ? (int64_t) slot_of[e] : e] = sum;
+                nhit += k;
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) nhit += __shfl_down(nhit, off, 64);
+    if (lane == 0 && nhit) atomicAdd(hits, nhit);
+}
+
+extern "C" int gmx_adamic_adar(gmx_graph_t* g, double* aa_host, gmx_stats_t* stats) {
+    GMX_REQUIRE(g && aa_host, "NULL argument");
+    if (stats) {
+        memset(stats, 0, sizeof(*stats));
+        stats->iterations = 1;
+    }
+    if (g->E == 0) return GMX_OK;
+    GMX_CHECK(tc_require_sorted_rows(g, "gmx_adamic_adar"));
+    const int64_t V = g->V, E = g->E;
+    int cap = AA_CAP, alone = AA_ALONE;
+    if (const char* s = getenv("GMX_AA_CAP")) cap = atoi(s) < 0 ? 0 : atoi(s) > AA_CAP ? AA_CAP : atoi(s);
+    if (const char* s = getenv("GMX_AA_ALONE")) alone = atoi(s) < 0 ? 0 : atoi(s);
+    dbuf<double> w, aa;
+    dbuf<int64_t> groups, grp_off;
+    dbuf<unsigned long long> ctr;   // [0] next work item, [1] common-neighbour hits
+    dbuf<char> tmp;
+    GMX_CHECK(w.alloc((size_t) V));
+    GMX_CHECK(aa.alloc((size_t) E));
+    GMX_CHECK(groups.alloc((size_t) V + 1));
+    GMX_CHECK(grp_off.alloc((size_t) V + 1));
+    GMX_CHECK(ctr.alloc(2));
+    size_t tb = 0;
+    GMX_HIP(rocprim::exclusive_scan(nullptr, tb, groups.p, grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), 0));
+    GMX_CHECK(tmp.alloc(tb));
+    hipEvent_t ev[4];
+    for (int i = 0; i < 4; i++) GMX_HIP(hipEventCreate(&ev[i]));
+    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_HIP(hipMemsetAsync(ctr.p, 0, 2 * sizeof(unsigned long long), 0));
+    GMX_HIP(hipMemsetAsync(groups.p + V, 0, sizeof(int64_t), 0));
+    hipLaunchKernelGGL(aa_weight_kernel, dim3(tc_grid(V)), dim3(TC_THREADS), 0, 0, (const int32_t*) g->begin.p, V, w.p, groups.p);
+    GMX_HIP(hipGetLastError());
+    GMX_HIP(rocprim::exclusive_scan((void*) tmp.p, tb, groups.p, grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), 0));
+    hipLaunchKernelGGL(aa_rows_kernel, dim3(256 * 8), dim3(AA_WAVES * 64), 0, 0, (const int32_t*) g->begin.p, (const int32_t*) g->node_idx.p,
+                       (const double*) w.p, (const int64_t*) grp_off.p, V, cap, alone, (const int32_t*) g->e_idx2idx.p, ctr.p, ctr.p + 1, aa.p);
+    GMX_HIP(hipGetLastError());
+    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_HIP(hipMemcpy(aa_host, aa.p, sizeof(double) * (size_t) E, hipMemcpyDeviceToHost));
+    GMX_HIP(hipEventRecord(ev[3], 0));
+    GMX_HIP(hipEventSynchronize(ev[3]));
+    unsigned long long h = 0;
+    GMX_HIP(hipMemcpy(&h, ctr.p + 1, sizeof(h), hipMemcpyDeviceToHost));
+    float kms = 0, dms = 0;
+    (void) hipEventElapsedTime(&kms, ev[0], ev[1]);
+    (void) hipEventElapsedTime(&dms, ev[2], ev[3]);
+    for (int i = 0; i < 4; i++) (void) hipEventDestroy(ev[i]);
+    if (stats) {
+        stats->kernel_ms = kms;
+        stats->d2h_ms = dms;
+        stats->edges_examined = (int64_t) h;
+    }
+    return GMX_OK;
+}

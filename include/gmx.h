@@ -97,8 +97,8 @@ int gmx_workspace_release(void);
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
  *     gmx_scc and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len is indexed by the stored slots);
- *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs and
- *     gmx_common_nbr_counts binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
+ *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
+ *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
  *     gm_common_neighbor_iter.h): GMX_ERR_STATE when the forward rows are not sorted.  With sorted forward rows and an
  *     unsorted reverse CSR, triangle counting takes the forward-only form of a GMX_GRAPH_NO_REVERSE graph. */
 int gmx_graph_upload(const gmx_edge_t* begin, const gmx_node_t* node_idx,
@@ -236,6 +236,22 @@ int gmx_triangle_counting_part(gmx_graph_t* g, int part, int nparts, int64_t* co
 int gmx_common_nbrs(gmx_graph_t* g, gmx_node_t s, gmx_node_t d, gmx_node_t* out, int64_t cap, int64_t* n);
 int gmx_common_nbr_counts(gmx_graph_t* g, const gmx_node_t* src, const gmx_node_t* dst, int64_t npairs, int64_t* counts);
 int gmx_triangle_counting_cn(gmx_graph_t* g, int64_t* count, gmx_stats_t* stats);
+
+/* adamicAdar(G, aa) (apps/src/adamicAdar.gm; driver apps/output_cpp/src/adamicAdar_main.cc:25), the application that
+ * computes with the iterator: for every forward edge slot e = (from -> to)
+ *     aa[e] = sum over the items n of gm_common_neighbor_iter(G, from, to) -- the slots of row(from), in slot order and
+ *             with their multiplicity, whose value occurs in row(to) -- of 1.0 / log((double) outdeg(n)),
+ * outdeg(n) = begin[n+1] - begin[n], in IEEE double without fast-math.  What the formula gives is what is returned: a
+ * common neighbour of out-degree 1 contributes +inf (the edge's value is +inf), one of out-degree 0 contributes -0.0, an
+ * edge without common neighbours gets exactly +0.0, and no value is NaN.  The order of the additions inside one edge's
+ * sum is the device's, not the slot order (a distinct value that row(from) repeats m times enters as m * its term), but
+ * it is fixed: the result is bit-identical from run to run, and within (k + 2) * 2^-52 relative of the slot-order sum
+ * for an edge with k items.  Repeated slots (from, to) of a multigraph get the same value.
+ * aa_host[E] is indexed like gmx_sssp's len: by the UPLOADED slots (through e_idx2idx when the upload sorted the rows).
+ * Only the forward CSR is read (a GMX_GRAPH_NO_REVERSE graph works); forward rows uploaded verbatim and out of order give
+ * GMX_ERR_STATE, as for the iterator.  E = 0: GMX_OK, nothing written.  stats: iterations = 1, kernel_ms = device time
+ * (weights, work list and the intersections), d2h_ms = download of aa, edges_examined = items over all slots (exact). */
+int gmx_adamic_adar(gmx_graph_t* g, double* aa_host /* [E] */, gmx_stats_t* stats);
 
 /* ---- device-resident PageRank stepping (bench.py / multi-GPU driver) ----
  * A gmx_pr_t owns the rows [row_lo,row_hi) of the (internally relabelled) graph
