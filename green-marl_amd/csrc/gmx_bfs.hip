@@ -1533,6 +1533,463 @@ extern "C" int gmx_sssp(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host
     return GMX_OK;
 }
 
+// ------------------------------------------------------------------ sssp_path: the shortest-path tree next to the lengths
+// The emitted `sssp_path` (/root/reference/apps/src/sssp_path.gm:1-30) is sssp's loop whose min= also records the winner:
+//     <s.dist_nxt; s.updated_nxt, s.prev> min= <n.dist + e.len; True, n>
+// Which of several equally short predecessors it records depends on the reference's thread timing.  The device returns a
+// fixed member of that set: distance and predecessor slot of a vertex are ONE 64-bit word,
+//     key[v] = (dist << 32) | device slot of the in-edge        (root: (0, NIL); unreached: (INT_MAX, NIL))
+// and relaxing slot e = n -> s offers (dist[n] + len[e], e) with one 64-bit unsigned atomicMin.  Ties in the distance are
+// offered too, so among the candidates at the final distance -- exactly the tight in-edges, each offered after its
+// source's last drop (a candidate that equals the final distance of s cannot come from a source above its own final
+// distance) -- the smallest slot wins whatever the order.  A zero-length edge may only win when it lowers the distance
+// strictly (compare-and-swap): the vertices of a zero-length cycle then take their predecessors in the order in which
+// they reached the distance, which has no cycle.  Lengths must be >= 0 (the word orders distances as unsigned).
+// The schedule has to keep one invariant: every vertex relaxes all its out-edges at least once after its last drop,
+// reading its current distance.  Two schedules do:
+//   round queue   gmx_sssp's: a vertex whose distance dropped in round r is relaxed in round r + 1;
+//   near / far    a drop below the threshold T goes to the next round's queue, the others to a far pile; when the queue
+//                 runs dry T advances by delta (further, when nothing lies below it) and the pile is filtered: entries
+//                 whose vertex is below the old T are stale (it was queued when it got there, and relaxed since), the
+//                 others go to the queue (below the new T) or stay, each vertex once.
+// stamp[v] = 2 * tag + (queued: 1, piled: 0) of the last time v entered either, tags rising from launch to launch.
+#define SP_NIL 0xFFFFFFFFu
+#define SP_WORD(d, e) (((unsigned long long) (uint32_t) (d) << 32) | (unsigned long long) (uint32_t) (e))
+// slots of bfs_counters::pad0 the far pile uses (same cache line as next_count: one claim per workgroup)
+#define SP_FAR_TAIL 0   // entries in the pile being written
+#define SP_FAR_NEAREST 1   // filter: max over the kept entries of (2^32 - distance); 0 = none kept
+#define SP_FAR_SPILL 2   // an entry did not fit (never, by the host's accounting): the call fails instead of writing
+
+__global__ void sp_init_kernel(unsigned long long* __restrict__ key, int32_t* __restrict__ stamp, int64_t V, int32_t root) {
+    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (; i < V; i += stride) {
+        key[i] = SP_WORD(i == root ? 0 : INT_MAX, SP_NIL);
+        stamp[i] = -1;
+    }
+}
+
+// out[0] = number of negative lengths, out[1] = sum of the lengths (one atomic per workgroup and value)
+__global__ void __launch_bounds__(BFS_THREADS)
+sp_len_check_kernel(const int32_t* __restrict__ len, int64_t E, unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long s_neg[BFS_THREADS / 64], s_sum[BFS_THREADS / 64];
+    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    unsigned long long neg = 0, sum = 0;
+    for (; i < E; i += stride) {
+        const int32_t l = len[i];
+        neg += l < 0;
+        sum += l < 0 ? 0ull : (unsigned long long) l;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        neg += __shfl_down(neg, o, 64);
+        sum += __shfl_down(sum, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_neg[threadIdx.x >> 6] = neg;
+        s_sum[threadIdx.x >> 6] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        neg = sum = 0;
+        for (int w = 0; w < BFS_THREADS / 64; w++) {
+            neg += s_neg[w];
+            sum += s_sum[w];
+        }
+        if (neg) atomicAdd(&out[0], neg);
+        if (sum) atomicAdd(&out[1], sum);
+    }
+}
+
+// the lanes of a wave that have a vertex for a workgroup's list append together
+__device__ __forceinline__ void sp_stage(bool on, int32_t v, int32_t* s_list, unsigned int* s_n, int lane) {
+    const unsigned long long mk = __ballot(on);
+    if (mk) {
+        const int leader = __ffsll((long long) mk) - 1;
+        unsigned int at = 0;
+        if (lane == leader) at = atomicAdd(s_n, (unsigned int) __popcll(mk));
+        at = __shfl(at, leader, 64);
+        if (on) s_list[at + __popcll(mk & ((1ULL << lane) - 1))] = v;
+    }
+}
+
+// sssp_relax_kernel's shape with the packed word.  NEARFAR: drops to threshold or above go to the far pile.
+template <bool NEARFAR>
+__global__ void __launch_bounds__(BFS_THREADS)
+sp_relax_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ node_idx, const int32_t* __restrict__ len,
+                const int32_t* __restrict__ cur_q, int64_t n, const int64_t* __restrict__ off, int64_t m, int32_t tag,
+                unsigned long long* key, int32_t* __restrict__ stamp, int32_t* __restrict__ next_q, int32_t* __restrict__ far_q,
+                unsigned long long far_cap, uint32_t threshold, bfs_counters* __restrict__ ctr, const int64_t* __restrict__ split) {
+    __shared__ int64_t s_off[BFS_ITEMS + 2];
+    __shared__ int32_t s_row[BFS_ITEMS + 2];
+    __shared__ uint32_t s_dist[BFS_ITEMS + 2];
+    __shared__ int32_t s_win[BFS_ITEMS];   // (one queue-tail claim per workgroup, as in sssp_relax_kernel)
+    __shared__ int32_t s_far[NEARFAR ? BFS_ITEMS : 1];
+    __shared__ unsigned int s_nwin, s_nfar;
+    __shared__ unsigned long long s_base, s_fbase;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) s_nwin = s_nfar = 0;
+    int64_t d0 = (int64_t) blockIdx.x * BFS_ITEMS, d1 = d0 + BFS_ITEMS;
+    if (d1 > n + m) d1 = n + m;
+    const int64_t v0 = split[blockIdx.x], v1 = split[blockIdx.x + 1], e0 = d0 - v0, e1 = d1 - v1;
+    const int nv = (int) (v1 - v0) + 1;
+    for (int i = tid; i < nv; i += BFS_THREADS) {
+        const int64_t vi = v0 + i;
+        s_off[i] = vi <= n ? off[vi < n ? vi : n] : m;
+        const int32_t v = vi < n ? cur_q[vi] : 0;
+        s_row[i] = vi < n ? begin[v] : 0;
+        s_dist[i] = vi < n ? (uint32_t) (key[v] >> 32) : 0u;   // the current distance (a later drop queues v again)
+    }
+    if (tid == 0) s_off[nv] = m + 1;
+    __syncthreads();
+    unsigned long long inspected = 0;
+    for (int64_t x = e0 + tid; x < e1; x += BFS_THREADS) {
+        int lo = 0, hi = nv - 1;
+        while (lo < hi) {
+            int mid = (lo + hi + 1) >> 1;
+            if (s_off[mid] <= x) lo = mid; else hi = mid - 1;
+        }
+        const int64_t e = (int64_t) s_row[lo] + (x - s_off[lo]);
+        const int32_t s = node_idx[e];
+        const int32_t l = len[e];
+        const uint32_t nd = s_dist[lo] + (uint32_t) l;
+        const unsigned long long cand = SP_WORD(nd, e);
+        inspected++;
+        // <s.dist_nxt; s.updated_nxt, s.prev> min= <n.dist + e.len; True, n>   (sssp_path.gm:21)
+        unsigned long long cur = key[s];   // (a stale copy is only higher: the atomic decides)
+        bool dropped = false;
+        if (l > 0) {
+            if (cand < cur) dropped = (uint32_t) (atomicMin(&key[s], cand) >> 32) > nd;   // equal distance: a smaller slot, no new work
+        } else {
+            while ((uint32_t) (cur >> 32) > nd) {   // zero length: only a strictly lower distance
+                const unsigned long long seen = atomicCAS(&key[s], cur, cand);
+                if (seen == cur) {
+                    dropped = true;
+                    break;
+                }
+                cur = seen;
+            }
+        }
+        bool to_queue = false, to_pile = false;
+        if (dropped) {
+            const bool near = !NEARFAR || nd < threshold;
+            const int32_t mark = 2 * tag + (near ? 1 : 0);
+            const bool first = atomicMax(&stamp[s], mark) < mark;   // (piled and then queued in one launch: both)
+            to_queue = first && near;
+            to_pile = first && !near;
+        }
+        sp_stage(to_queue, s, s_win, &s_nwin, lane);
+        if (NEARFAR) sp_stage(to_pile, s, s_far, &s_nfar, lane);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) inspected += __shfl_down(inspected, o, 64);
+    if (lane == 0) bfs_count(ctr, inspected, 0);
+    __syncthreads();
+    const unsigned int nwin = s_nwin, nfar = NEARFAR ? s_nfar : 0u;
+    if (nwin == 0 && nfar == 0) return;   // (workgroup-uniform)
+    if (tid == 0) {
+        if (nwin) s_base = atomicAdd(&ctr->next_count, (unsigned long long) nwin);
+        if (nfar) s_fbase = atomicAdd(&ctr->pad0[SP_FAR_TAIL], (unsigned long long) nfar);
+    }
+    __syncthreads();
+    for (unsigned int i = tid; i < nwin; i += BFS_THREADS) next_q[s_base + i] = s_win[i];
+    if (NEARFAR && nfar) {
+        if (s_fbase + nfar <= far_cap) {
+            for (unsigned int i = tid; i < nfar; i += BFS_THREADS) far_q[s_fbase + i] = s_far[i];
+        } else if (tid == 0) {
+            ctr->pad0[SP_FAR_SPILL] = 1ull;
+        }
+    }
+}
+
+// The far pile when the threshold moves from t_old to t_new (or, with t_new == t_old, when the pile is only to be made
+// smaller): see the schedule above.  near_q takes at most one entry per vertex, far_out at most min(n, V).
+__global__ void __launch_bounds__(BFS_THREADS)
+sp_refilter_kernel(const int32_t* __restrict__ far_in, int64_t n, const unsigned long long* __restrict__ key, int32_t* __restrict__ stamp,
+                   int32_t tag, uint32_t t_old, uint32_t t_new, int32_t* __restrict__ near_q, int32_t* __restrict__ far_out,
+                   bfs_counters* __restrict__ ctr) {
+    __shared__ int32_t s_win[BFS_ITEMS];
+    __shared__ int32_t s_far[BFS_ITEMS];
+    __shared__ unsigned int s_nwin, s_nfar;
+    __shared__ unsigned long long s_base, s_fbase, s_nearest;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) {
+        s_nwin = s_nfar = 0;
+        s_nearest = 0;
+    }
+    __syncthreads();
+    unsigned long long nearest = 0;
+    const int64_t i0 = (int64_t) blockIdx.x * BFS_ITEMS;
+    for (int k = 0; k < BFS_ITEMS / BFS_THREADS; k++) {   // (every lane runs every step: whole waves at the ballots)
+        const int64_t i = i0 + tid + (int64_t) k * BFS_THREADS;
+        bool to_queue = false, to_pile = false;
+        int32_t v = 0;
+        if (i < n) {
+            v = far_in[i];
+            const uint32_t d = (uint32_t) (key[v] >> 32);
+            if (d >= t_old) {
+                const bool near = d < t_new;
+                const int32_t mark = 2 * tag + (near ? 1 : 0);
+                const bool first = atomicMax(&stamp[v], mark) < mark;
+                to_queue = first && near;
+                to_pile = first && !near;
+                if (to_pile) {
+                    const unsigned long long inv = 0x100000000ull - (unsigned long long) d;
+                    nearest = inv > nearest ? inv : nearest;
+                }
+            }
+        }
+        sp_stage(to_queue, v, s_win, &s_nwin, lane);
+        sp_stage(to_pile, v, s_far, &s_nfar, lane);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long t = __shfl_down(nearest, o, 64);
+        nearest = t > nearest ? t : nearest;
+    }
+    if (lane == 0 && nearest) atomicMax(&s_nearest, nearest);
+    __syncthreads();
+    const unsigned int nwin = s_nwin, nfar = s_nfar;
+    if (nwin == 0 && nfar == 0) return;   // (workgroup-uniform)
+    if (tid == 0) {
+        if (nwin) s_base = atomicAdd(&ctr->next_count, (unsigned long long) nwin);
+        if (nfar) {
+            s_fbase = atomicAdd(&ctr->pad0[SP_FAR_TAIL], (unsigned long long) nfar);
+            atomicMax(&ctr->pad0[SP_FAR_NEAREST], s_nearest);
+        }
+    }
+    __syncthreads();
+    for (unsigned int i = tid; i < nwin; i += BFS_THREADS) near_q[s_base + i] = s_win[i];
+    for (unsigned int i = tid; i < nfar; i += BFS_THREADS) far_out[s_fbase + i] = s_far[i];
+}
+
+// one thread per vertex splits the word: dist, the predecessor slot as an UPLOADED slot, and the row that holds it
+__global__ void sp_finish_kernel(const unsigned long long* __restrict__ key, const int32_t* __restrict__ begin,
+                                 const int32_t* __restrict__ e_idx2idx /* NULL: the device slots are the uploaded ones */, int64_t V,
+                                 int32_t* __restrict__ dist, int32_t* __restrict__ prev_node, int32_t* __restrict__ prev_edge) {
+    int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (; v < V; v += stride) {
+        const unsigned long long k = key[v];
+        const uint32_t e = (uint32_t) k;
+        dist[v] = (int32_t) (k >> 32);
+        int32_t pn = -1, pe = -1;
+        if (e != SP_NIL) {
+            int64_t lo = 0, hi = V - 1;   // the last row that starts at or before e (the empty rows before it start there too)
+            while (lo < hi) {
+                const int64_t mid = (lo + hi + 1) >> 1;
+                if ((uint32_t) begin[mid] <= e) lo = mid; else hi = mid - 1;
+            }
+            pn = (int32_t) lo;
+            pe = e_idx2idx ? e_idx2idx[e] : (int32_t) e;
+        }
+        prev_node[v] = pn;
+        prev_edge[v] = pe;
+    }
+}
+
+// GMX_SSSP_PATH_SCHEDULE = round | nearfar (read at every call); GMX_SSSP_DELTA = the near / far threshold step
+static bool sp_use_nearfar() {
+    const char* s = getenv("GMX_SSSP_PATH_SCHEDULE");
+    if (s && !strcmp(s, "nearfar")) return true;
+    if (s && !strcmp(s, "round")) return false;
+    return false;
+}
+
+extern "C" int gmx_sssp_path(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host, int32_t* dist_host, gmx_node_t* prev_node_host,
+                             gmx_edge_t* prev_edge_host, gmx_stats_t* stats) {
+    GMX_REQUIRE(g && dist_host && prev_node_host, "NULL argument");
+    GMX_REQUIRE(len_host || g->E == 0, "len is NULL");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const int64_t V = g->V, E = g->E;
+    if (V == 0) return GMX_OK;
+    const bool root_ok = root >= 0 && root < V;
+    const bool nearfar = sp_use_nearfar();
+    const size_t far_cap = nearfar ? 2 * (size_t) V : 0;   // a launch adds at most V entries to a pile of at most V
+    dbuf<unsigned long long> key, chk;
+    dbuf<int32_t> stamp, q0, q1, deg, len, far0, far1, out;
+    dbuf<int64_t> off, split;
+    dbuf<bfs_counters> ctr;
+    dbuf<char> scan_tmp;
+    size_t scan_bytes = 0;
+    GMX_CHECK(split.alloc((size_t) ((V + E) / BFS_ITEMS + 3)));
+    GMX_CHECK(key.alloc((size_t) V));
+    GMX_CHECK(chk.alloc(2));
+    GMX_CHECK(stamp.alloc((size_t) V));
+    GMX_CHECK(q0.alloc((size_t) V));
+    GMX_CHECK(q1.alloc((size_t) V));
+    GMX_CHECK(deg.alloc((size_t) V));
+    GMX_CHECK(off.alloc((size_t) V + 2));
+    GMX_CHECK(ctr.alloc(1));
+    GMX_CHECK(len.alloc((size_t) (E ? E : 1)));
+    GMX_CHECK(out.alloc(3 * (size_t) V));
+    if (nearfar) {
+        GMX_CHECK(far0.alloc(far_cap));
+        GMX_CHECK(far1.alloc(far_cap));
+    }
+    GMX_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, deg.p, off.p + 1, (size_t) V, rocprim::plus<int64_t>(), 0));
+    GMX_CHECK(scan_tmp.alloc(scan_bytes));
+    ev_guard evg[6];
+    hipEvent_t ev[6];
+    for (int i = 0; i < 6; i++) {
+        GMX_CHECK(evg[i].create());
+        ev[i] = evg[i].e;
+    }
+    pinned_guard<bfs_counters> pg_ctr;
+    pinned_guard<int64_t> pg_mf;
+    GMX_CHECK(pg_ctr.alloc());
+    GMX_CHECK(pg_mf.alloc());
+    bfs_counters* h_ctr = pg_ctr.p;
+    int64_t* h_mf = pg_mf.p;
+    // the property: copied in, checked on the device copy (negative lengths are refused), brought into the order of the
+    // sorted rows when the upload sorted them
+    GMX_HIP(hipEventRecord(ev[2], 0));
+    unsigned long long h_chk[2] = {0, 0};
+    if (E) {
+        GMX_HIP(hipMemcpy(len.p, len_host, sizeof(int32_t) * (size_t) E, hipMemcpyHostToDevice));
+        GMX_HIP(hipMemsetAsync(chk.p, 0, 2 * sizeof(unsigned long long), 0));
+        hipLaunchKernelGGL(sp_len_check_kernel, dim3(grid_for(E)), dim3(BFS_THREADS), 0, 0, (const int32_t*) len.p, E, chk.p);
+        GMX_HIP(hipGetLastError());
+        GMX_HIP(hipMemcpy(h_chk, chk.p, sizeof(h_chk), hipMemcpyDeviceToHost));
+        GMX_REQUIRE(h_chk[0] == 0, "len holds %llu negative value(s): gmx_sssp_path needs len >= 0", h_chk[0]);
+    }
+    dbuf<int32_t> len_sorted;
+    if (E && g->e_idx2idx.p) {
+        GMX_CHECK(len_sorted.alloc((size_t) E));
+        hipLaunchKernelGGL(gather_by_order_kernel, dim3(grid_for(E)), dim3(BFS_THREADS), 0, 0, (const int32_t*) len.p,
+                           (const int32_t*) g->e_idx2idx.p, E, len_sorted.p);
+    }
+    const int32_t* len_dev = len_sorted.p ? len_sorted.p : len.p;
+    GMX_HIP(hipEventRecord(ev[3], 0));
+    // near / far: delta = 32 * mean length / mean out-degree (a queue round then holds about a wave's worth of edges per
+    // vertex of the band), at least 1
+    uint32_t delta = 1;
+    if (nearfar) {
+        double dl = E ? 32.0 * ((double) h_chk[1] / (double) E) / ((double) E / (double) V) : 1.0;
+        const char* s = getenv("GMX_SSSP_DELTA");
+        if (s && atof(s) >= 1.0) dl = atof(s);
+        delta = dl < 1.0 ? 1u : dl > 1073741824.0 ? (1u << 30) : (uint32_t) dl;
+    }
+    const uint32_t T_ALL = 0x80000000u;   // above every distance
+    uint32_t T = nearfar ? delta : T_ALL;
+    GMX_HIP(hipEventRecord(ev[0], 0));
+    hipLaunchKernelGGL(sp_init_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, key.p, stamp.p, V, root_ok ? root : -1);
+    int64_t cur_count = 0, queued = 0, far_n = 0;
+    unsigned long long edges = 0;
+    int32_t rounds = 0, tag = 0;
+    int32_t* cur_q = q0.p;
+    int32_t* next_q = q1.p;
+    int32_t* far_cur = far0.p;
+    int32_t* far_alt = far1.p;
+    if (root_ok) {
+        GMX_HIP(hipMemcpy(q0.p, &root, sizeof(int32_t), hipMemcpyHostToDevice));
+        cur_count = queued = 1;
+    }
+    GMX_HIP(hipMemsetAsync(ctr.p, 0, sizeof(bfs_counters), 0));
+    // filter the pile far_cur[0 .. far_n) into cur_q (which is empty, or untouched when t_new == t_old) and far_alt
+    auto refilter = [&](uint32_t t_old, uint32_t t_new, int64_t* near_n, uint32_t* nearest) -> int {
+        GMX_HIP(hipMemsetAsync(&ctr.p->next_count, 0, (2 + SP_FAR_NEAREST + 1) * sizeof(unsigned long long), 0));
+        hipLaunchKernelGGL(sp_refilter_kernel, dim3((unsigned) ((far_n + BFS_ITEMS - 1) / BFS_ITEMS)), dim3(BFS_THREADS), 0, 0,
+                           (const int32_t*) far_cur, far_n, (const unsigned long long*) key.p, stamp.p, tag, t_old, t_new, cur_q, far_alt, ctr.p);
+        GMX_HIP(hipGetLastError());
+        GMX_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof(bfs_counters), hipMemcpyDeviceToHost, 0));
+        GMX_HIP(hipStreamSynchronize(0));
+        tag++;
+        *near_n = (int64_t) h_ctr->next_count;
+        far_n = (int64_t) h_ctr->pad0[SP_FAR_TAIL];
+        *nearest = h_ctr->pad0[SP_FAR_NEAREST] ? (uint32_t) (0x100000000ull - h_ctr->pad0[SP_FAR_NEAREST]) : 0u;
+        int32_t* t = far_cur;
+        far_cur = far_alt;
+        far_alt = t;
+        return GMX_OK;
+    };
+    for (;;) {
+        while (cur_count > 0) {
+            if (nearfar && far_n > V) {   // room for this round's (at most V) new entries: drop the stale ones and the repeats
+                int64_t none = 0;
+                uint32_t unused = 0;
+                GMX_CHECK(refilter(T, T, &none, &unused));
+                GMX_REQUIRE(none == 0 && far_n <= V, "gmx_sssp_path: far pile accounting");
+            }
+            GMX_HIP(hipMemsetAsync(&ctr.p->next_count, 0, sizeof(unsigned long long), 0));   // (`edges` and the pile's tail run on)
+            hipLaunchKernelGGL(bfs_degree_kernel, dim3(grid_for(cur_count)), dim3(BFS_THREADS), 0, 0, g->begin.p, cur_q, cur_count, deg.p);
+            size_t tb = scan_bytes;
+            GMX_HIP(rocprim::inclusive_scan(scan_tmp.p, tb, deg.p, off.p + 1, (size_t) cur_count, rocprim::plus<int64_t>(), 0));
+            GMX_HIP(hipMemsetAsync(off.p, 0, sizeof(int64_t), 0));
+            GMX_HIP(hipMemcpyAsync(h_mf, off.p + cur_count, sizeof(int64_t), hipMemcpyDeviceToHost, 0));
+            GMX_HIP(hipStreamSynchronize(0));
+            const int64_t m_f = *h_mf;
+            const int64_t nb = (cur_count + m_f + BFS_ITEMS - 1) / BFS_ITEMS;
+            if (nb > 0) {
+                hipLaunchKernelGGL(bfs_merge_split_kernel, dim3((unsigned) ((nb + 1 + BFS_THREADS - 1) / BFS_THREADS)), dim3(BFS_THREADS), 0, 0,
+                                   (const int64_t*) off.p, cur_count, m_f, nb, split.p);
+                if (nearfar)
+                    hipLaunchKernelGGL(sp_relax_kernel<true>, dim3((unsigned) nb), dim3(BFS_THREADS), 0, 0, g->begin.p, g->node_idx.p, len_dev,
+                                       cur_q, cur_count, off.p, m_f, tag, key.p, stamp.p, next_q, far_cur, (unsigned long long) far_cap, T,
+                                       ctr.p, (const int64_t*) split.p);
+                else
+                    hipLaunchKernelGGL(sp_relax_kernel<false>, dim3((unsigned) nb), dim3(BFS_THREADS), 0, 0, g->begin.p, g->node_idx.p, len_dev,
+                                       cur_q, cur_count, off.p, m_f, tag, key.p, stamp.p, next_q, (int32_t*) nullptr, 0ull, T, ctr.p,
+                                       (const int64_t*) split.p);
+            }
+            GMX_HIP(hipGetLastError());
+            GMX_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof(bfs_counters), hipMemcpyDeviceToHost, 0));
+            GMX_HIP(hipStreamSynchronize(0));
+            const bfs_counters& h = *h_ctr;
+            unsigned long long found_unused = 0;
+            cur_count = (int64_t) h.next_count;
+            far_n = (int64_t) h.pad0[SP_FAR_TAIL];
+            GMX_REQUIRE(h.pad0[SP_FAR_SPILL] == 0 && far_n <= (int64_t) far_cap, "gmx_sssp_path: far pile overflow");
+            bfs_totals(h, &edges, &found_unused);
+            queued += cur_count;
+            int32_t* t = cur_q;
+            cur_q = next_q;
+            next_q = t;
+            rounds++;
+            tag++;
+        }
+        if (far_n == 0) break;
+        // the queue ran dry: advance the threshold; when nothing lies below the new one, to just above the nearest entry
+        uint32_t nearest = 0;
+        const uint32_t t_old = T;
+        T = T > T_ALL - delta ? T_ALL : T + delta;
+        GMX_CHECK(refilter(t_old, T, &cur_count, &nearest));
+        if (cur_count == 0 && far_n > 0) {
+            const uint64_t up = ((uint64_t) nearest / delta + 1) * (uint64_t) delta;
+            const uint32_t t_prev = T;
+            T = up > T_ALL ? T_ALL : (uint32_t) up;
+            GMX_CHECK(refilter(t_prev, T, &cur_count, &nearest));
+            GMX_REQUIRE(cur_count > 0, "gmx_sssp_path: threshold accounting");
+        }
+        queued += cur_count;
+    }
+    hipLaunchKernelGGL(sp_finish_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, (const unsigned long long*) key.p, (const int32_t*) g->begin.p,
+                       (const int32_t*) g->e_idx2idx.p, V, out.p, out.p + V, out.p + 2 * V);
+    GMX_HIP(hipGetLastError());
+    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_HIP(hipEventSynchronize(ev[1]));
+    GMX_HIP(hipEventRecord(ev[4], 0));
+    GMX_HIP(hipMemcpy(dist_host, out.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
+    GMX_HIP(hipMemcpy(prev_node_host, out.p + V, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
+    if (prev_edge_host) GMX_HIP(hipMemcpy(prev_edge_host, out.p + 2 * V, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
+    GMX_HIP(hipEventRecord(ev[5], 0));
+    GMX_HIP(hipEventSynchronize(ev[5]));
+    if (stats) {
+        float ms = 0, hms = 0, dms = 0;
+        (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
+        (void) hipEventElapsedTime(&hms, ev[2], ev[3]);
+        (void) hipEventElapsedTime(&dms, ev[4], ev[5]);
+        stats->iterations = rounds;
+        stats->kernel_ms = ms;
+        stats->h2d_ms = hms;
+        stats->d2h_ms = dms;
+        stats->edges_examined = (int64_t) edges;
+        stats->vertices_reached = queued;   // queue entries over all rounds (a vertex may re-enter), the root's included
+    }
+    return GMX_OK;
+}
+
 // ------------------------------------------------------------------ BFS object: InBFS / InReverse
 // The device counterpart of gm_bfs_template<level_t = short, ..., save_child> (gm_bfs_template.h:14-312) as the
 // emitted `InBFS(v: G.Nodes From s) {..} InReverse {..}` uses it (gm_cpp_gen_bfs.cc:88-275):

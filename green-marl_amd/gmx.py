@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_sssp", "gmx_scc", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -106,6 +106,7 @@ def lib():
         L.gmx_bc.argtypes = [vp, vp, i32, C.c_int, vp, C.POINTER(Stats)]
         L.gmx_triangle_counting.argtypes = [vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_sssp.argtypes = [vp, i32, vp, vp, C.POINTER(Stats)]
+        L.gmx_sssp_path.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(Stats)]
         L.gmx_scc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_avg_teen_cnt.argtypes = [vp, vp, i32, vp, C.POINTER(C.c_float), C.POINTER(Stats)]
         L.gmx_conduct.argtypes = [vp, vp, i32, C.POINTER(C.c_float), C.POINTER(Stats)]
@@ -326,6 +327,19 @@ class Graph:
         _ck(lib().gmx_sssp(self._h, int(root), length.ctypes.data if self.E else None, dist.ctypes.data, C.byref(st)))
         return dist, st.as_dict()
 
+    def sssp_path(self, length, root=0):
+        """sssp_path(G, dist, len, root, prev): length[E] int32 >= 0 by uploaded forward edge slot -- returns (dist[int32],
+        prev_node[int32], prev_edge[int32], stats).  prev_* are -1 for the root and unreached vertices, otherwise the
+        canonical tight in-edge (the smallest uploaded slot where every tight in-edge has positive length) and its source."""
+        length = _i32(length)
+        assert len(length) == self.E
+        V = self.V
+        dist, prev_node, prev_edge = (np.zeros(max(V, 1), np.int32) for _ in range(3))
+        st = Stats()
+        _ck(lib().gmx_sssp_path(self._h, int(root), length.ctypes.data if self.E else None, dist.ctypes.data,
+                                prev_node.ctypes.data, prev_edge.ctypes.data, C.byref(st)))
+        return dist[:V], prev_node[:V], prev_edge[:V], st.as_dict()
+
     def scc(self):
         """kosaraju(G, mem): strongly connected components -- returns (comp[int32], count, stats).  comp numbers the
         components canonically: 0 .. count-1 in increasing order of each component's smallest vertex id."""
@@ -401,6 +415,22 @@ class Graph:
         st = Stats()
         _ck(lib().gmx_triangle_counting_part(self._h, part, nparts, C.byref(t), C.byref(st)))
         return t.value, st.as_dict()
+
+
+def path_from_prev(prev_node, begin, end):
+    """get_path of sssp_path.gm on Graph.sssp_path's prev_node: the vertices begin .. end of the tree path, or [] when end
+    has no predecessor (unreached, or the root itself).  begin must lie on end's path to the root."""
+    path = []
+    if prev_node[end] < 0:
+        return path
+    t = int(end)
+    while t != begin:
+        path.append(t)
+        t = int(prev_node[t])
+        if t < 0 or len(path) > len(prev_node):
+            raise GmxError("begin %d is not on the path from the root to %d" % (begin, end))
+    path.append(t)
+    return path[::-1]
 
 
 def default_pr_options(V, nranks=1):

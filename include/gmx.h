@@ -204,6 +204,31 @@ int gmx_bc(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_roo
  * stats: iterations = relaxation rounds, h2d_ms = upload of len, vertices_reached = queue entries over all rounds. */
 int gmx_sssp(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host, int32_t* dist_host, gmx_stats_t* stats);
 
+/* sssp_path(G, dist, len, root, prev) (apps/src/sssp_path.gm:1-30; driver apps/output_cpp/src/sssp_path_main.cc:44): gmx_sssp's
+ * lengths together with a shortest-path tree.  len_host[E] is indexed like gmx_sssp's len, by the UPLOADED forward slots
+ * (through e_idx2idx when the upload sorted the rows), and every value must be >= 0: a negative one gives GMX_ERR_ARG
+ * (checked on the device copy before the traversal; the reference would run Bellman-Ford on it).  Path sums must stay
+ * below INT_MAX, as for gmx_sssp.
+ *   dist_host[V]       exactly what gmx_sssp returns for the same arguments; INT_MAX = unreached; a root outside [0, V)
+ *                      gives INT_MAX everywhere.
+ *   prev_node_host[V], prev_edge_host[V] (the latter may be NULL; sssp_path_adj.gm's prev_edge)
+ *                      -1 (gm_graph::NIL_NODE / NIL_EDGE) for the root and for unreached vertices; otherwise a TIGHT
+ *                      in-edge n -> v: prev_edge[v] = e as an UPLOADED forward slot, prev_node[v] = n its source, with
+ *                      dist[n] != INT_MAX and dist[n] + len[e] == dist[v].  Following prev_node from any reached vertex
+ *                      arrives at the root in fewer than V steps: prev is a shortest-path tree.
+ * Canonical choice: the reference's prev depends on thread timing (the first writer of the round in which dist_nxt[v]
+ * reached its final value).  Here, where every tight in-edge of v has positive length, prev_edge[v] is the SMALLEST
+ * uploaded slot among them (uploaded slots are grouped by source, so prev_node[v] is the smallest tight predecessor): with
+ * len >= 1 everywhere the whole output is fixed, bit-identical from run to run and independent of the schedule.  A vertex
+ * with a tight in-edge of length 0 gets some tight in-edge, with only the tree property guaranteed.  This tree may differ
+ * from the one a particular run of the reference produces; both are shortest-path trees of the same dist.
+ * Only the forward CSR is read (a GMX_GRAPH_NO_REVERSE graph works), in any row order.  V = 0: GMX_OK.  E = 0: len_host
+ * may be NULL.  stats as for gmx_sssp (iterations = relaxation rounds, kernel_ms, h2d_ms = upload and check of len,
+ * edges_examined, vertices_reached = queue entries over all rounds), and d2h_ms = download of the three arrays.
+ * GMX_SSSP_PATH_SCHEDULE = round | nearfar picks the schedule (DESIGN.md 4.2b'); the results do not depend on it. */
+int gmx_sssp_path(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host /* [E] */, int32_t* dist_host /* [V] */,
+                  gmx_node_t* prev_node_host /* [V] */, gmx_edge_t* prev_edge_host /* [V] or NULL */, gmx_stats_t* stats);
+
 /* avg_teen_cnt(G, age, teen_cnt, K) (apps/src/avg_teen_cnt.gm; driver avg_teen_cnt_main.cc:24) and
  * conduct(G, member, num) (apps/src/conduct.gm; driver conduct_main.cc:45): count-reductions over neighbours
  * with the caller's int32 node property; integers exact, the returned float formed by the emitted expression. */
