@@ -388,6 +388,7 @@ void gmx_warm_modules() {
     gmx_touch_pr_cold();
     gmx_touch_bfs();
     gmx_touch_scc();
+    gmx_touch_comm();
 }
 
 static int check_sizes(int64_t V, int64_t E) {

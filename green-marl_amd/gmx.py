@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -108,6 +108,7 @@ def lib():
         L.gmx_sssp.argtypes = [vp, i32, vp, vp, C.POINTER(Stats)]
         L.gmx_sssp_path.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(Stats)]
         L.gmx_scc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_communities.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_avg_teen_cnt.argtypes = [vp, vp, i32, vp, C.POINTER(C.c_float), C.POINTER(Stats)]
         L.gmx_conduct.argtypes = [vp, vp, i32, C.POINTER(C.c_float), C.POINTER(Stats)]
         L.gmx_graph_reverse_edge_map.argtypes = [vp, vp]
@@ -347,6 +348,14 @@ class Graph:
         n, st = C.c_int64(0), Stats()
         _ck(lib().gmx_scc(self._h, comp.ctypes.data, C.byref(n), C.byref(st)))
         return comp[:self.V], int(n.value), st.as_dict()
+
+    def communities(self, max_rounds=1000):
+        """communities(G, comm): label propagation under the canonical tie rule and schedule (gmx.h) -- returns
+        (comm[int32], rounds, converged, stats).  comm holds vertex ids; converged is 1 when comm is a fixpoint."""
+        comm = np.zeros(max(self.V, 1), np.int32)
+        rounds, conv, st = C.c_int32(0), C.c_int32(0), Stats()
+        _ck(lib().gmx_communities(self._h, int(max_rounds), comm.ctypes.data, C.byref(rounds), C.byref(conv), C.byref(st)))
+        return comm[:self.V], int(rounds.value), int(conv.value), st.as_dict()
 
     def avg_teen_cnt(self, age, K):
         """avg_teen_cnt(G, age, teen_cnt, K) -- returns (avg float32, teen_cnt[int32], stats)."""

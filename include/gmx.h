@@ -244,6 +244,37 @@ int gmx_conduct(gmx_graph_t* g, const int32_t* member_host, int32_t num, float* 
  * kernel_ms = device time, d2h_ms = download of comp. */
 int gmx_scc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, gmx_stats_t* stats);
 
+/* communities(G, comm) (apps/src/communities.gm:1-24; driver apps/output_cpp/src/communities_main.cc:19): label-propagation
+ * community detection.  comm[x] = x; then every vertex x counts the labels of its out-neighbours, once per slot (a
+ * repeated slot counts again, a self loop counts x's own label), keeps its label if that label has the highest count, and
+ * otherwise takes the most frequent one -- until nothing changes.  Three things the reference leaves to its map class and
+ * to thread timing are fixed here:
+ *   tie        among the labels with the highest count the SMALLEST is taken (what gm_map_small's ordered iteration gives,
+ *              gm_map.h:165-177), and only when the vertex's own label is not among them;
+ *   no edges   a vertex without out-neighbours keeps its label (GetMaxKey on an empty map is undefined in the reference);
+ *   schedule   the reference updates comm in place from many threads.  Here round r = 0, 1, ... is two half-rounds: vertex v
+ *              belongs to half  h(v, r) = fmix32(uint32(v) ^ (uint32(r) * 0x9E3779B9u)) & 1,  fmix32 the murmur3 finaliser
+ *              (h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16).  Half 0 runs first, then
+ *              half 1; a half-round evaluates its vertices against one snapshot of comm and all its new labels are stored
+ *              together before the next half-round starts.  This is one interleaving of the reference's loop, it is
+ *              deterministic, and it converges where plain synchronous rounds swap labels for ever (a star, a 2-cycle).
+ * Rounds run until one changes no label or max_rounds rounds have run (a directed chain needs about V of them under any
+ * schedule).  *rounds = rounds that changed a label; *converged = 1 exactly when comm_host is a fixpoint of the rule (every
+ * vertex with out-neighbours holds a label whose count over its row is the row's maximum) -- what any terminating run of
+ * the reference returns -- decided, when max_rounds cut the run, by one more evaluation pass that writes nothing.
+ * comm_host[V]: labels are vertex ids in [0, V); bit-identical from run to run (integer counts only).
+ * max_rounds < 0 or comm_host == NULL: GMX_ERR_ARG.  rounds, converged, stats may be NULL.  V = 0: GMX_OK.  E = 0 or
+ * max_rounds = 0: the identity labels, converged as defined.  Rows are read in any order, with repeats: no GMX_ERR_STATE
+ * for unsorted rows.  Only the forward CSR is needed; with a reverse CSR only the vertices whose rows saw a label change
+ * are evaluated again (GMX_COMM_WORKLIST=0 turns that off), which changes the work and not the result: a
+ * GMX_GRAPH_NO_REVERSE graph gives identical arrays.  GMX_COMM_WAVE_MIN, GMX_COMM_BLOCK_MIN and GMX_COMM_LDS_SLOTS (read
+ * at every call) move the row-length thresholds between the three evaluation kernels and size their tables (DESIGN.md
+ * 4.2e); the results do not depend on them.
+ * stats: iterations = *rounds, kernel_ms = device time from the first launch to the last commit, d2h_ms = download of
+ * comm, vertices_reached = vertex evaluations over all half-rounds, edges_examined = slots read by them. */
+int gmx_communities(gmx_graph_t* g, int32_t max_rounds, gmx_node_t* comm_host /* [V] */,
+                    int32_t* rounds, int32_t* converged, gmx_stats_t* stats);
+
 /* triangle_counting(G) with the emitted multiplicity rule. */
 int gmx_triangle_counting(gmx_graph_t* g, int64_t* count, gmx_stats_t* stats);
 /* Multi-GPU form (replicated CSR, final all-reduce of int64): the count contributed by part
