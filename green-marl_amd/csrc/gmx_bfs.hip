@@ -17,7 +17,7 @@
 //                are reported as a bitmap (one ballot per wave), applied to dist[] and reused as the
 //                next level's frontier -- and, with several GPUs, exchanged slice by slice.
 // Integer only: bit-exact against the CPU result by construction.
-#include "gmx_internal.h"
+#include "gmx_frontier.h"
 
 #include <float.h>
 #include <limits.h>
@@ -26,24 +26,6 @@
 #include <chrono>
 #include <rocprim/rocprim.hpp>
 
-#define BFS_THREADS 256
-
-// Statistics that thousands of waves add to (edges inspected, vertices found by a bottom-up level) are spread over
-// BFS_SHARDS cache lines and summed by the host after the read-back: atomics on ONE line retire at ~90 per
-// microsecond device-wide, and two such adds per wave were 0.37 ms of a 0.39 ms bottom-up level at RMAT-20 (and
-// ~0.7 ms per bottom-up level at RMAT-26).  Both run on: a level's count is the difference to the previous total.
-#define BFS_SHARDS 64
-struct bfs_counters {
-    unsigned long long next_count;     // top-down: tail of the next queue = vertices discovered in this level
-    unsigned long long next_edges;     // their out-edges: the next level's merge-path length and the input of the
-                                       // direction decision, known without a pass over the new queue
-    unsigned long long pad0[14];
-    struct {
-        unsigned long long edges;      // edges inspected so far
-        unsigned long long found;      // vertices found by bottom-up levels so far
-        unsigned long long pad[14];
-    } shard[BFS_SHARDS];
-};
 // A level's totals for the host: summed on the device and written straight into pinned host memory, the level's tag
 // last.  The host spins on the tag -- a stream synchronisation takes ~20 us to wake up, which at small scales was
 // most of a level.
@@ -51,11 +33,6 @@ struct bfs_level_totals {
     unsigned long long next_count, next_edges, edges, found;
     volatile unsigned long long tag;
 };
-__device__ __forceinline__ void bfs_count(bfs_counters* __restrict__ ctr, unsigned long long edges, unsigned long long found) {
-    const int sh = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (BFS_SHARDS - 1);
-    if (edges) atomicAdd(&ctr->shard[sh].edges, edges);
-    if (found) atomicAdd(&ctr->shard[sh].found, found);
-}
 __global__ void bfs_totals_kernel(const bfs_counters* __restrict__ ctr, bfs_level_totals* __restrict__ out, unsigned long long tag) {
     const int lane = threadIdx.x;   // 64 threads, one shard each
     unsigned long long e = ctr->shard[lane].edges, f = ctr->shard[lane].found;
@@ -73,16 +50,6 @@ __global__ void bfs_totals_kernel(const bfs_counters* __restrict__ ctr, bfs_leve
         out->tag = tag;
     }
 }
-static void bfs_totals(const bfs_counters& h, unsigned long long* edges, unsigned long long* found) {
-    unsigned long long e = 0, f = 0;
-    for (int i = 0; i < BFS_SHARDS; i++) {
-        e += h.shard[i].edges;
-        f += h.shard[i].found;
-    }
-    *edges = e;
-    *found = f;
-}
-
 // everything a traversal starts from, in one launch: dist[], both bitmaps, the counters, the root in the first queue
 // and its out-degree on its way to the host (next_edges of "level -1", tag 0 of the run)
 __global__ void bfs_init_kernel(int32_t* __restrict__ dist, int64_t V, int32_t root, unsigned long long* __restrict__ bm0,
@@ -103,8 +70,6 @@ __global__ void bfs_init_kernel(int32_t* __restrict__ dist, int64_t V, int32_t r
     for (int64_t w = i; w < words; w += stride) bm0[w] = bm1[w] = 0ull;
     for (; i < V; i += stride) dist[i] = (i == root) ? 0 : INT_MAX;
 }
-
-#define BFS_ITEMS 2048   // merge-path items (frontier vertices + their out-edges) per workgroup
 
 __global__ void bfs_degree_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ q, int64_t n,
                                   int32_t* __restrict__ deg) {
@@ -182,12 +147,30 @@ __global__ void bfs_merge_split_kernel(const int64_t* __restrict__ off, int64_t 
     if (k > nb) return;
     int64_t dk = k * BFS_ITEMS;
     if (dk > n + m) dk = n + m;
-    int64_t lo = dk > m ? dk - m : 0, hi = dk < n ? dk : n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid + 1] <= dk - mid - 1) lo = mid + 1; else hi = mid;
-    }
-    split[k] = lo;
+    split[k] = frontier_diagonal(off, n, m, dk);
+}
+
+int gmx_frontier_scan_alloc(frontier_scan* s, size_t max_n, size_t max_tiles) {
+    GMX_CHECK(s->deg.alloc(max_n));
+    GMX_CHECK(s->off.alloc(max_n + 2));
+    if (max_tiles) GMX_CHECK(s->split.alloc(max_tiles));
+    GMX_HIP(rocprim::inclusive_scan(nullptr, s->scan_bytes, s->deg.p, s->off.p + 1, max_n, rocprim::plus<int64_t>(), 0));
+    return s->scan_tmp.alloc(s->scan_bytes);
+}
+
+int gmx_frontier_offsets(const int32_t* begin, const int32_t* q, int64_t n, frontier_scan* s, int64_t* h_m, bool with_split) {
+    hipLaunchKernelGGL(bfs_degree_kernel, dim3(grid_for(n)), dim3(BFS_THREADS), 0, 0, begin, q, n, s->deg.p);
+    size_t tb = s->scan_bytes;
+    GMX_HIP(rocprim::inclusive_scan(s->scan_tmp.p, tb, s->deg.p, s->off.p + 1, (size_t) n, rocprim::plus<int64_t>(), 0));
+    GMX_HIP(hipMemsetAsync(s->off.p, 0, sizeof(int64_t), 0));
+    if (!h_m) return GMX_OK;
+    GMX_HIP(hipMemcpyAsync(h_m, s->off.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, 0));
+    GMX_HIP(hipStreamSynchronize(0));
+    const int64_t nb = frontier_tiles(n, *h_m);
+    if (with_split && nb > 0)
+        hipLaunchKernelGGL(bfs_merge_split_kernel, dim3((unsigned) ((nb + 1 + BFS_THREADS - 1) / BFS_THREADS)), dim3(BFS_THREADS), 0, 0,
+                           (const int64_t*) s->off.p, n, *h_m, nb, s->split.p);
+    return GMX_OK;
 }
 
 // off[0..n] = exclusive prefix sums of the frontier degrees (off[n] = frontier edges).
@@ -210,27 +193,9 @@ bfs_topdown_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict_
         s_nwin = 0;
         s_deg = 0;
     }
-    if (tid < 2) {   // merge-path split of diagonals k*ITEMS and (k+1)*ITEMS
-        int64_t dk = ((int64_t) blockIdx.x + tid) * BFS_ITEMS;
-        if (dk > n + m) dk = n + m;
-        int64_t lo = dk > m ? dk - m : 0, hi = dk < n ? dk : n;
-        while (lo < hi) {
-            int64_t mid = (lo + hi) >> 1;
-            if (off[mid + 1] <= dk - mid - 1) lo = mid + 1; else hi = mid;
-        }
-        s_split[tid][0] = lo;
-        s_split[tid][1] = dk - lo;
-    }
-    __syncthreads();
-    const int64_t v0 = s_split[0][0], e0 = s_split[0][1], v1 = s_split[1][0], e1 = s_split[1][1];
-    const int nv = (int) (v1 - v0) + 1;   // frontier slots touched (the last one may be partial / == n)
-    for (int i = tid; i < nv; i += BFS_THREADS) {
-        int64_t vi = v0 + i;
-        s_off[i] = vi <= n ? off[vi < n ? vi : n] : m;
-        s_row[i] = vi < n ? begin[cur_q[vi]] : 0;
-    }
-    if (tid == 0) s_off[nv] = m + 1;   // sentinel
-    __syncthreads();
+    const frontier_tile t = frontier_tile_search(off, n, m, s_split);
+    const int64_t e0 = t.e0, e1 = t.e1;
+    const int nv = frontier_stage(t, begin, cur_q, n, off, m, s_off, s_row, [](int, int32_t, bool) {});
     unsigned long long inspected = 0, deg = 0;
     // A thread's edges (at most BFS_ITEMS / BFS_THREADS) go through the four dependent accesses of an edge -- its slot,
     // dist[] of the neighbour, the atomicMin, the winner's out-degree -- TOGETHER, one access kind at a time: edge by
@@ -244,12 +209,7 @@ bfs_topdown_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict_
             const int64_t x = e0 + tid + (int64_t) k * BFS_THREADS;
             valid[k] = x < e1;
             const int64_t xc = valid[k] ? x : e0;   // (loads stay unconditional: a slot that exists)
-            // frontier slot of edge x: last i with s_off[i] <= x
-            int lo = 0, hi = nv - 1;
-            while (lo < hi) {
-                int mid = (lo + hi + 1) >> 1;
-                if (s_off[mid] <= xc) lo = mid; else hi = mid - 1;
-            }
+            const int lo = frontier_slot(s_off, nv, xc);
             sv[k] = node_idx[(int64_t) s_row[lo] + (xc - s_off[lo])];
             inspected += valid[k];
         }
@@ -271,18 +231,7 @@ bfs_topdown_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict_
         }
 #pragma unroll
         for (int k = 0; k < K; k++) {
-            const unsigned long long mw = __ballot(won[k]);
-            if (mw) {
-                const int lane = tid & 63;
-                const int leader = __ffsll((long long) mw) - 1;
-                unsigned int at = 0;
-                if (lane == leader) at = atomicAdd(&s_nwin, (unsigned int) __popcll(mw));
-                at = __shfl(at, leader, 64);
-                if (won[k]) {
-                    s_win[at + __popcll(mw & ((1ULL << lane) - 1))] = sv[k];
-                    deg += (unsigned long long) dg[k];
-                }
-            }
+            wave_append(won[k], sv[k], s_win, &s_nwin, tid & 63, [&] { deg += (unsigned long long) dg[k]; });
         }
     }
 #pragma unroll
@@ -297,12 +246,9 @@ bfs_topdown_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict_
     __syncthreads();
     const unsigned int nwin = s_nwin;
     if (nwin == 0) return;   // (workgroup-uniform)
-    if (tid == 0) {
-        s_base = atomicAdd(&ctr->next_count, (unsigned long long) nwin);
+    frontier_flush(s_win, nwin, &ctr->next_count, next_q, &s_base, [&] {
         if (s_deg) atomicAdd(&ctr->next_edges, s_deg);
-    }
-    __syncthreads();
-    for (unsigned int i = tid; i < nwin; i += BFS_THREADS) next_q[s_base + i] = s_win[i];
+    });
 }
 
 // A SPARSE frontier (about one out-edge per vertex: the tail levels of a traversal): one vertex per lane, no degree pass,
@@ -315,17 +261,8 @@ __device__ __forceinline__ void bfs_sparse_visit(bool on, int32_t s, int32_t lev
                                                  unsigned long long& deg) {
     bool won = false;
     if (on && dist[s] == INT_MAX) won = atomicMin(&dist[s], level + 1) == INT_MAX;
-    const unsigned long long mw = __ballot(won);
-    if (mw) {   // (the lanes that are here together claim together)
-        const int leader = __ffsll((long long) mw) - 1;
-        unsigned long long at = 0;
-        if (lane == leader) at = atomicAdd(&ctr->next_count, (unsigned long long) __popcll(mw));
-        at = __shfl(at, leader, 64);
-        if (won) {
-            next_q[at + __popcll(mw & ((1ULL << lane) - 1))] = s;
-            deg += (unsigned long long) (begin[s + 1] - begin[s]);
-        }
-    }
+    // (the lanes that are here together claim together)
+    wave_append(won, s, next_q, &ctr->next_count, lane, [&] { deg += (unsigned long long) (begin[s + 1] - begin[s]); });
 }
 __global__ void __launch_bounds__(BFS_THREADS)
 bfs_topdown_sparse_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ node_idx, const int32_t* __restrict__ cur_q,
@@ -349,7 +286,7 @@ bfs_topdown_sparse_kernel(const int32_t* __restrict__ begin, const int32_t* __re
     }
     unsigned long long pending = __ballot(own_e < e);
     while (pending) {
-        const int src = __ffsll((long long) pending) - 1;
+        const int src = __builtin_ctzll(pending);
         pending &= pending - 1;
         const int32_t rb = __shfl(own_e, src, 64), re = __shfl(e, src, 64);
         for (int32_t x0 = rb; x0 < re; x0 += 64) {
@@ -414,17 +351,7 @@ bfs_first_level_kernel(const int32_t* __restrict__ begin, const int32_t* __restr
             dist[sv[k]] = level + 1;
             if (bm32) atomicOr(&bm32[sv[k] >> 5], 1u << (sv[k] & 31));
         }
-        const unsigned long long mw = __ballot(won[k]);
-        if (mw) {
-            const int leader = __ffsll((long long) mw) - 1;
-            unsigned int at = 0;
-            if (lane == leader) at = atomicAdd(&s_nwin, (unsigned int) __popcll(mw));
-            at = __shfl(at, leader, 64);
-            if (won[k]) {
-                s_win[at + __popcll(mw & ((1ULL << lane) - 1))] = sv[k];
-                deg += (unsigned long long) dg[k];
-            }
-        }
+        wave_append(won[k], sv[k], s_win, &s_nwin, lane, [&] { deg += (unsigned long long) dg[k]; });
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -438,12 +365,9 @@ bfs_first_level_kernel(const int32_t* __restrict__ begin, const int32_t* __restr
     __syncthreads();
     const unsigned int nwin = s_nwin;
     if (nwin == 0) return;   // (workgroup-uniform)
-    if (tid == 0) {
-        s_base = atomicAdd(&ctr->next_count, (unsigned long long) nwin);
+    frontier_flush(s_win, nwin, &ctr->next_count, next_q, &s_base, [&] {
         if (s_deg) atomicAdd(&ctr->next_edges, s_deg);
-    }
-    __syncthreads();
-    for (unsigned int i = tid; i < nwin; i += BFS_THREADS) next_q[s_base + i] = s_win[i];
+    });
 }
 
 // frontier bitmap of a level straight from dist[] (coalesced reads, one __ballot per 64 vertices, no atomics)
@@ -476,16 +400,7 @@ __global__ void bfs_level_queue_kernel(const int32_t* __restrict__ dist, int64_t
     const int64_t stride = (int64_t) gridDim.x * blockDim.x;
     const int64_t vend = (V + 63) / 64 * 64;
     for (; v < vend; v += stride) {
-        const bool in = v < V && dist[v] == level;
-        const unsigned long long m = __ballot(in);
-        if (m) {
-            const int lane = threadIdx.x & 63;
-            const int leader = __ffsll((long long) m) - 1;
-            unsigned long long base = 0;
-            if (lane == leader) base = atomicAdd(qcount, (unsigned long long) __popcll(m));
-            base = __shfl(base, leader, 64);
-            if (in) q[base + __popcll(m & ((1ULL << lane) - 1))] = (int32_t) v;
-        }
+        wave_append(v < V && dist[v] == level, (int32_t) v, q, qcount, threadIdx.x & 63);
     }
 }
 
@@ -525,7 +440,7 @@ bfs_bitmap_queue_kernel(const unsigned long long* __restrict__ bm64, int64_t wor
     for (int64_t w = lo + threadIdx.x; w < hi; w += BFS_THREADS) {
         unsigned long long m = bm64[w];
         while (m) {
-            const int b = __ffsll((long long) m) - 1;
+            const int b = __builtin_ctzll(m);
             m &= m - 1;
             const int64_t v = w * 64 + b;
             q[at++] = (int32_t) v;
@@ -565,13 +480,6 @@ __global__ void bfs_edges_reached_kernel(const int32_t* __restrict__ dist, const
     }
 }
 
-static int grid_for(int64_t n, int block = BFS_THREADS, int max_blocks = 256 * 8) {
-    int64_t b = (n + block - 1) / block;
-    if (b < 1) b = 1;
-    if (b > max_blocks) b = max_blocks;
-    return (int) b;
-}
-
 // ------------------------------------------------------------------ the traversal as a stepping object (1..N ranks)
 // replicated CSR, 1-D vertex ranges.  The levels that matter at scale are the
 // bottom-up ones (the few levels that reach most of the graph), and those partition by DESTINATION: rank k
@@ -584,10 +492,8 @@ struct gmx_bfs {
     gmx_graph* g = nullptr;
     int rank = 0, nranks = 1;
     int64_t V = 0, slice_words = 0, words = 0;   // bitmap words (64 vertices each): per rank, total (padded)
-    dbuf<int32_t> dist, q0, q1, deg;
-    dbuf<int64_t> off;
-    dbuf<char> scan_tmp;
-    size_t scan_bytes = 0;
+    dbuf<int32_t> dist, q0, q1;
+    frontier_scan fs;                 // the queue's out-degrees and their prefix sums (merge-path offsets)
     dbuf<unsigned long long> cand;    // unvisited vertices with in-edges, kept from one bottom-up level to the next
     bool cand_valid = false;
     dbuf<unsigned long long> bm[2];   // frontier / found, swapped after every bottom-up level
@@ -608,15 +514,9 @@ struct gmx_bfs {
     int32_t* next_q = nullptr;
     // per-level read-backs (frontier size, frontier edges) go through pinned host memory: a level costs two
     // host round trips, and with pageable memory each is a staged copy -- at RMAT-24 that was most of the time
-    bfs_counters* h_ctr = nullptr;
-    bfs_level_totals* h_tot = nullptr;   // pinned; written by bfs_totals_kernel
+    gmx_pinned<bfs_level_totals> h_tot;   // written by bfs_totals_kernel
     unsigned long long tot_tag = 0;
-    int64_t* h_mf = nullptr;
-    ~gmx_bfs() {
-        if (h_ctr) (void) hipHostFree(h_ctr);
-        if (h_tot) (void) hipHostFree(h_tot);
-        if (h_mf) (void) hipHostFree(h_mf);
-    }
+    gmx_pinned<int64_t> h_mf;
 };
 
 // The in-neighbour a bottom-up level tries first: of the first BFS_HINT_SCAN entries of the in-row the one with most
@@ -859,7 +759,7 @@ bfs_bottomup_part_kernel(const int32_t* __restrict__ r_begin, const int32_t* __r
                 }
                 unsigned long long pending = __ballot(rest_e > rest_b);
                 while (pending) {
-                    const int src = __ffsll((long long) pending) - 1;
+                    const int src = __builtin_ctzll(pending);
                     pending &= pending - 1;
                     const int32_t rb = __shfl(rest_b, src, 64), re = __shfl(rest_e, src, 64);
                     bool hit = false;
@@ -997,31 +897,14 @@ extern "C" int gmx_bfs_create(gmx_graph_t* g, int rank, int nranks, gmx_bfs_t** 
     b->words = b->slice_words * nranks;
     const size_t V1 = (size_t) (g->V ? g->V : 1);
     int st = GMX_OK;
-    if ((st = b->dist.alloc(V1)) || (st = b->q0.alloc(V1)) || (st = b->q1.alloc(V1)) || (st = b->deg.alloc(V1)) ||
-        (st = b->off.alloc(V1 + 2)) || (st = b->ctr.alloc(1)) || (st = b->qcount.alloc(1)) ||
+    if ((st = b->dist.alloc(V1)) || (st = b->q0.alloc(V1)) || (st = b->q1.alloc(V1)) || (st = gmx_frontier_scan_alloc(&b->fs, V1, 0)) ||
+        (st = b->ctr.alloc(1)) || (st = b->qcount.alloc(1)) ||
         (st = b->bm[0].alloc((size_t) b->words)) || (st = b->bm[1].alloc((size_t) b->words)) || (st = b->cand.alloc((size_t) b->words)) ||
-        (st = b->hub_bits.alloc(BFS_HUBS / 64))) {
+        (st = b->hub_bits.alloc(BFS_HUBS / 64)) || (st = b->h_tot.alloc()) || (st = b->h_mf.alloc())) {
         delete b;
         return st;
     }
-    if (hipHostMalloc((void**) &b->h_tot, sizeof(bfs_level_totals), hipHostMallocDefault) != hipSuccess) {
-        gmx_set_error("hipHostMalloc failed");
-        delete b;
-        return GMX_ERR_NOMEM;
-    }
-    memset(b->h_tot, 0, sizeof(bfs_level_totals));
-    if (hipHostMalloc((void**) &b->h_ctr, sizeof(bfs_counters), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**) &b->h_mf, sizeof(int64_t), hipHostMallocDefault) != hipSuccess) {
-        delete b;
-        gmx_set_error("bfs: pinned host allocation failed");
-        return GMX_ERR_HIP;
-    }
-    if (rocprim::inclusive_scan(nullptr, b->scan_bytes, b->deg.p, b->off.p + 1, V1, rocprim::plus<int64_t>(), 0) != hipSuccess ||
-        (st = b->scan_tmp.alloc(b->scan_bytes))) {
-        delete b;
-        gmx_set_error("bfs: scan setup failed");
-        return st ? st : GMX_ERR_HIP;
-    }
+    memset(b->h_tot.p, 0, sizeof(bfs_level_totals));
     *out = b;
     return GMX_OK;
 }
@@ -1036,10 +919,10 @@ extern "C" int gmx_bfs_free(gmx_bfs_t* b) {
 static int bfs_wait_totals(gmx_bfs* b, unsigned long long tag) {
     const auto t0 = std::chrono::steady_clock::now();
     unsigned long long spins = 0;
-    while (b->h_tot->tag != tag) {
+    while (b->h_tot.p->tag != tag) {
         if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
             GMX_HIP(hipStreamSynchronize(0));
-            GMX_REQUIRE(b->h_tot->tag == tag, "bfs: the level's totals did not arrive");
+            GMX_REQUIRE(b->h_tot.p->tag == tag, "bfs: the level's totals did not arrive");
             break;
         }
     }
@@ -1055,7 +938,7 @@ extern "C" int gmx_bfs_start(gmx_bfs_t* b, gmx_node_t root) {
     const unsigned long long tag = ++b->tot_tag;
     hipLaunchKernelGGL(bfs_init_kernel, dim3(grid_for(V > (int64_t) (sizeof(bfs_counters) / 8) ? V : (int64_t) (sizeof(bfs_counters) / 8))), dim3(BFS_THREADS), 0, 0,
                        b->dist.p, V, root_ok ? (int32_t) root : -1, b->bm[0].p, b->bm[1].p, b->words, b->ctr.p, b->q0.p,
-                       (const int32_t*) b->g->begin.p, b->h_tot, tag);
+                       (const int32_t*) b->g->begin.p, b->h_tot.p, tag);
     GMX_HIP(hipGetLastError());
     b->level = 0;
     b->cur_count = b->reached = root_ok ? 1 : 0;
@@ -1072,19 +955,14 @@ extern "C" int gmx_bfs_start(gmx_bfs_t* b, gmx_node_t root) {
     b->cur_edges = -1;
     b->found_total = 0;
     GMX_CHECK(bfs_wait_totals(b, tag));
-    if (root_ok) b->cur_edges = (int64_t) b->h_tot->next_edges;
+    if (root_ok) b->cur_edges = (int64_t) b->h_tot.p->next_edges;
     return GMX_OK;
 }
 
-// frontier out-degrees -> off[], returns their sum (the same helper steps as in gmx_hop_dist)
+// frontier out-degrees -> off[], returns their sum
 static int bfs_frontier_edges(gmx_bfs* b, int64_t* m_f) {
-    hipLaunchKernelGGL(bfs_degree_kernel, dim3(grid_for(b->cur_count)), dim3(BFS_THREADS), 0, 0, b->g->begin.p, b->cur_q, b->cur_count, b->deg.p);
-    size_t tb = b->scan_bytes;
-    GMX_HIP(rocprim::inclusive_scan(b->scan_tmp.p, tb, b->deg.p, b->off.p + 1, (size_t) b->cur_count, rocprim::plus<int64_t>(), 0));
-    GMX_HIP(hipMemsetAsync(b->off.p, 0, sizeof(int64_t), 0));
-    GMX_HIP(hipMemcpyAsync(b->h_mf, b->off.p + b->cur_count, sizeof(int64_t), hipMemcpyDeviceToHost, 0));
-    GMX_HIP(hipStreamSynchronize(0));
-    *m_f = *b->h_mf;
+    GMX_CHECK(gmx_frontier_offsets(b->g->begin.p, b->cur_q, b->cur_count, &b->fs, b->h_mf.p, false));
+    *m_f = *b->h_mf.p;
     return GMX_OK;
 }
 
@@ -1155,10 +1033,10 @@ extern "C" int gmx_bfs_step_begin(gmx_bfs_t* b, int* needs_exchange) {
                                    (const unsigned long long*) b->bm[b->fr].p, (V + 63) / 64, b->cur_q, b->qcount.p,
                                    (const int32_t*) g->begin.p, b->ctr.p);
                 const unsigned long long tag = ++b->tot_tag;
-                hipLaunchKernelGGL(bfs_totals_kernel, dim3(1), dim3(64), 0, 0, (const bfs_counters*) b->ctr.p, b->h_tot, tag);
+                hipLaunchKernelGGL(bfs_totals_kernel, dim3(1), dim3(64), 0, 0, (const bfs_counters*) b->ctr.p, b->h_tot.p, tag);
                 GMX_HIP(hipGetLastError());
                 GMX_CHECK(bfs_wait_totals(b, tag));
-                m_f = (int64_t) b->h_tot->next_edges;   // the offsets follow below, without a read-back
+                m_f = (int64_t) b->h_tot.p->next_edges;   // the offsets follow below, without a read-back
             } else {
                 hipLaunchKernelGGL(bfs_level_queue_kernel, dim3(grid_for(V, BFS_THREADS, 256 * 16)), dim3(BFS_THREADS), 0, 0,
                                    (const int32_t*) b->dist.p, V, b->level, b->cur_q, b->qcount.p);
@@ -1206,20 +1084,17 @@ extern "C" int gmx_bfs_step_begin(gmx_bfs_t* b, int* needs_exchange) {
         if (!have_off) {   // merge-path offsets of the queue
             if (b->cur_count <= BFS_SMALL_SCAN) {
                 hipLaunchKernelGGL(bfs_degree_scan_small_kernel, dim3(1), dim3(1024), 0, 0, g->begin.p, (const int32_t*) b->cur_q,
-                                   (int) b->cur_count, b->off.p, b->ctr.p);
+                                   (int) b->cur_count, b->fs.off.p, b->ctr.p);
                 cleared = true;
             } else {
-                hipLaunchKernelGGL(bfs_degree_kernel, dim3(grid_for(b->cur_count)), dim3(BFS_THREADS), 0, 0, g->begin.p, b->cur_q, b->cur_count, b->deg.p);
-                size_t tb = b->scan_bytes;
-                GMX_HIP(rocprim::inclusive_scan(b->scan_tmp.p, tb, b->deg.p, b->off.p + 1, (size_t) b->cur_count, rocprim::plus<int64_t>(), 0));
-                GMX_HIP(hipMemsetAsync(b->off.p, 0, sizeof(int64_t), 0));
+                GMX_CHECK(gmx_frontier_offsets(g->begin.p, b->cur_q, b->cur_count, &b->fs, nullptr, false));
             }
         }
         if (!cleared) GMX_HIP(hipMemsetAsync(&b->ctr.p->next_count, 0, 2 * sizeof(unsigned long long), 0));
-        const int64_t nb = (b->cur_count + m_f + BFS_ITEMS - 1) / BFS_ITEMS;
+        const int64_t nb = frontier_tiles(b->cur_count, m_f);
         if (nb > 0)
             hipLaunchKernelGGL(bfs_topdown_kernel, dim3((unsigned) nb), dim3(BFS_THREADS), 0, 0,
-                               g->begin.p, g->node_idx.p, b->cur_q, b->cur_count, b->off.p, m_f, b->level, b->dist.p, b->next_q, b->ctr.p);
+                               g->begin.p, g->node_idx.p, b->cur_q, b->cur_count, b->fs.off.p, m_f, b->level, b->dist.p, b->next_q, b->ctr.p);
         int32_t* t = b->cur_q;
         b->cur_q = b->next_q;
         b->next_q = t;
@@ -1253,11 +1128,11 @@ extern "C" int gmx_bfs_step_end(gmx_bfs_t* b, int64_t* next_count) {
         b->pending_bottom_up = false;
     }
     const unsigned long long tag = ++b->tot_tag;
-    hipLaunchKernelGGL(bfs_totals_kernel, dim3(1), dim3(64), 0, 0, (const bfs_counters*) b->ctr.p, b->h_tot, tag);
+    hipLaunchKernelGGL(bfs_totals_kernel, dim3(1), dim3(64), 0, 0, (const bfs_counters*) b->ctr.p, b->h_tot.p, tag);
     GMX_HIP(hipGetLastError());
     GMX_CHECK(bfs_wait_totals(b, tag));
-    struct { unsigned long long next_count, next_edges; } h = {b->h_tot->next_count, b->h_tot->next_edges};
-    const unsigned long long edges = b->h_tot->edges, found = b->h_tot->found;
+    struct { unsigned long long next_count, next_edges; } h = {b->h_tot.p->next_count, b->h_tot.p->next_edges};
+    const unsigned long long edges = b->h_tot.p->edges, found = b->h_tot.p->found;
     // a top-down level leaves its queue tail in next_count, a bottom-up level its finds in the running total
     if (getenv("GMX_BFS_DEBUG"))
         fprintf(stderr, "gmx bfs: level %d %s: frontier %lld -> inspected %llu, next frontier %lld\n", b->level, b->cur_edges == -2 ? "top-down" : "bottom-up",
@@ -1291,8 +1166,8 @@ extern "C" int gmx_hop_dist(gmx_graph_t* g, gmx_node_t root, int32_t* dist_host,
     if (g->V == 0) return GMX_OK;
     if (!g->bfs_cache) GMX_CHECK(gmx_bfs_create(g, 0, 1, &g->bfs_cache));   // graph preprocessing, like the reverse CSR
     gmx_bfs_t* b = g->bfs_cache;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (hipEvent_t& e : ev) (void) hipEventCreate(&e);
+    gmx_event ev[4];
+    for (gmx_event& e : ev) GMX_CHECK(e.create());
     int st = GMX_OK;
     (void) hipEventRecord(ev[0], 0);
     if ((st = gmx_bfs_start(b, root)) == GMX_OK) {
@@ -1326,669 +1201,9 @@ extern "C" int gmx_hop_dist(gmx_graph_t* g, gmx_node_t root, int32_t* dist_host,
             stats->edges_reached = (int64_t) edges_reached;
         }
     }
-    for (hipEvent_t e : ev)
-        if (e) (void) hipEventDestroy(e);
     return st;
 }
 
-// ------------------------------------------------------------------ sssp
-// The emitted `sssp` (/root/reference/apps/src/sssp.gm:1-30) is hop_dist's loop with an edge property:
-//     <s.dist_nxt; s.updated_nxt> min= <n.dist + e.len; True>     e = the out-edge slot being walked
-// until nothing changes.  dist[v] is the length of a shortest path over out-edges (INT_MAX: unreachable) --
-// unique, so the device is free to relax asynchronously: the updated vertices form a queue, their out-edges
-// are cut by merge-path exactly as in the top-down BFS level, every edge does atomicMin(dist[s], dist[n] +
-// len[e]) in place, and a vertex whose distance dropped enters the next queue once per round (round stamp).
-// Integer only: bit-exact against the CPU result.
-__global__ void __launch_bounds__(BFS_THREADS)
-sssp_relax_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ node_idx, const int32_t* __restrict__ len,
-                  const int32_t* __restrict__ cur_q, int64_t n, const int64_t* __restrict__ off, int64_t m,
-                  int32_t round, int32_t* __restrict__ dist, int32_t* __restrict__ stamp, int32_t* __restrict__ next_q,
-                  bfs_counters* __restrict__ ctr, const int64_t* __restrict__ split) {
-    __shared__ int64_t s_off[BFS_ITEMS + 2];
-    __shared__ int32_t s_row[BFS_ITEMS + 2];
-    __shared__ int32_t s_dist[BFS_ITEMS + 2];
-    __shared__ int32_t s_win[BFS_ITEMS];   // (one queue-tail claim per workgroup, as in bfs_topdown_kernel)
-    __shared__ unsigned int s_nwin;
-    __shared__ unsigned long long s_base;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_nwin = 0;
-    // merge-path split of the diagonals k * ITEMS and (k + 1) * ITEMS (bfs_merge_split_kernel): (rows consumed, edges consumed)
-    int64_t d0 = (int64_t) blockIdx.x * BFS_ITEMS, d1 = d0 + BFS_ITEMS;
-    if (d1 > n + m) d1 = n + m;
-    const int64_t v0 = split[blockIdx.x], v1 = split[blockIdx.x + 1], e0 = d0 - v0, e1 = d1 - v1;
-    const int nv = (int) (v1 - v0) + 1;
-    for (int i = tid; i < nv; i += BFS_THREADS) {
-        const int64_t vi = v0 + i;
-        s_off[i] = vi <= n ? off[vi < n ? vi : n] : m;
-        const int32_t v = vi < n ? cur_q[vi] : 0;
-        s_row[i] = vi < n ? begin[v] : 0;
-        s_dist[i] = vi < n ? dist[v] : 0;      // may already be lower than when v was queued: even better
-    }
-    if (tid == 0) s_off[nv] = m + 1;
-    __syncthreads();
-    unsigned long long inspected = 0;
-    for (int64_t x = e0 + tid; x < e1; x += BFS_THREADS) {
-        int lo = 0, hi = nv - 1;
-        while (lo < hi) {
-            int mid = (lo + hi + 1) >> 1;
-            if (s_off[mid] <= x) lo = mid; else hi = mid - 1;
-        }
-        const int64_t e = (int64_t) s_row[lo] + (x - s_off[lo]);
-        const int32_t s = node_idx[e];
-        const int32_t nd = s_dist[lo] + len[e];
-        inspected++;
-        bool won = false;
-        if (nd < dist[s] && nd < atomicMin(&dist[s], nd)) won = atomicExch(&stamp[s], round) != round;
-        const unsigned long long mk = __ballot(won);
-        if (mk) {
-            const int lane = threadIdx.x & 63;
-            const int leader = __ffsll((long long) mk) - 1;
-            unsigned int at = 0;
-            if (lane == leader) at = atomicAdd(&s_nwin, (unsigned int) __popcll(mk));
-            at = __shfl(at, leader, 64);
-            if (won) s_win[at + __popcll(mk & ((1ULL << lane) - 1))] = s;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) inspected += __shfl_down(inspected, o, 64);
-    if ((tid & 63) == 0) bfs_count(ctr, inspected, 0);
-    __syncthreads();
-    const unsigned int nwin = s_nwin;
-    if (nwin == 0) return;   // (workgroup-uniform)
-    if (tid == 0) s_base = atomicAdd(&ctr->next_count, (unsigned long long) nwin);
-    __syncthreads();
-    for (unsigned int i = tid; i < nwin; i += BFS_THREADS) next_q[s_base + i] = s_win[i];
-}
-
-__global__ void sssp_init_kernel(int32_t* __restrict__ dist, int32_t* __restrict__ stamp, int64_t V, int32_t root) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    for (; i < V; i += stride) {
-        dist[i] = (i == root) ? 0 : INT_MAX;
-        stamp[i] = -1;
-    }
-}
-
-// hipEvents / pinned words that are released on every return path
-struct ev_guard {
-    hipEvent_t e = nullptr;
-    ~ev_guard() { if (e) (void) hipEventDestroy(e); }
-    int create() { GMX_HIP(hipEventCreate(&e)); return GMX_OK; }
-};
-template <typename T>
-struct pinned_guard {
-    T* p = nullptr;
-    ~pinned_guard() { if (p) (void) hipHostFree(p); }
-    int alloc() { GMX_HIP(hipHostMalloc((void**) &p, sizeof(T), hipHostMallocDefault)); return GMX_OK; }
-};
-
-// dst[j] = src[order[j]]: an edge property given by uploaded slot, brought into the order of the sorted rows
-__global__ void gather_by_order_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ order, int64_t n, int32_t* __restrict__ dst) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    for (; i < n; i += stride) dst[i] = src[order[i]];
-}
-
-extern "C" int gmx_sssp(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host, int32_t* dist_host, gmx_stats_t* stats) {
-    GMX_REQUIRE(g && dist_host, "NULL argument");
-    GMX_REQUIRE(len_host || g->E == 0, "len is NULL");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    const int64_t V = g->V;
-    if (V == 0) return GMX_OK;
-    const bool root_ok = root >= 0 && root < V;
-    dbuf<int32_t> dist, stamp, q0, q1, deg, len;
-    dbuf<int64_t> off, split;
-    dbuf<bfs_counters> ctr;
-    dbuf<char> scan_tmp;
-    size_t scan_bytes = 0;
-    GMX_CHECK(split.alloc((size_t) ((V + g->E) / BFS_ITEMS + 3)));   // one entry per merge-path diagonal of a round
-    GMX_CHECK(dist.alloc((size_t) V));
-    GMX_CHECK(stamp.alloc((size_t) V));
-    GMX_CHECK(q0.alloc((size_t) V));
-    GMX_CHECK(q1.alloc((size_t) V));
-    GMX_CHECK(deg.alloc((size_t) V));
-    GMX_CHECK(off.alloc((size_t) V + 2));
-    GMX_CHECK(ctr.alloc(1));
-    GMX_CHECK(len.alloc((size_t) (g->E ? g->E : 1)));
-    GMX_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, deg.p, off.p + 1, (size_t) V, rocprim::plus<int64_t>(), 0));
-    GMX_CHECK(scan_tmp.alloc(scan_bytes));
-    ev_guard evg[4];
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; i++) {
-        GMX_CHECK(evg[i].create());
-        ev[i] = evg[i].e;
-    }
-    GMX_HIP(hipEventRecord(ev[2], 0));
-    if (g->E) GMX_HIP(hipMemcpy(len.p, len_host, sizeof(int32_t) * (size_t) g->E, hipMemcpyHostToDevice));   // the property is the caller's
-    dbuf<int32_t> len_sorted;
-    if (g->E && g->e_idx2idx.p) {
-        // the rows were sorted on upload: len[] is indexed by the caller's (unsorted) slots, the kernel walks the sorted ones
-        GMX_CHECK(len_sorted.alloc((size_t) g->E));
-        hipLaunchKernelGGL(gather_by_order_kernel, dim3(grid_for(g->E)), dim3(BFS_THREADS), 0, 0, (const int32_t*) len.p,
-                           (const int32_t*) g->e_idx2idx.p, g->E, len_sorted.p);
-    }
-    const int32_t* len_dev = len_sorted.p ? len_sorted.p : len.p;
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventRecord(ev[0], 0));
-    hipLaunchKernelGGL(sssp_init_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, dist.p, stamp.p, V, root_ok ? root : -1);
-    int64_t cur_count = 0, requeued = 0;
-    unsigned long long edges = 0;
-    int32_t round = 0;
-    int32_t* cur_q = q0.p;
-    int32_t* next_q = q1.p;
-    if (root_ok) {
-        GMX_HIP(hipMemcpy(q0.p, &root, sizeof(int32_t), hipMemcpyHostToDevice));
-        cur_count = 1;
-    }
-    // per-round read-backs through pinned memory (two host round trips per round, dozens of rounds)
-    pinned_guard<bfs_counters> pg_ctr;
-    pinned_guard<int64_t> pg_mf;
-    GMX_CHECK(pg_ctr.alloc());
-    GMX_CHECK(pg_mf.alloc());
-    bfs_counters* h_ctr = pg_ctr.p;
-    int64_t* h_mf = pg_mf.p;
-    GMX_HIP(hipMemsetAsync(ctr.p, 0, sizeof(bfs_counters), 0));
-    while (cur_count > 0) {
-        GMX_HIP(hipMemsetAsync(&ctr.p->next_count, 0, sizeof(unsigned long long), 0));   // `edges` keeps accumulating
-        hipLaunchKernelGGL(bfs_degree_kernel, dim3(grid_for(cur_count)), dim3(BFS_THREADS), 0, 0, g->begin.p, cur_q, cur_count, deg.p);
-        size_t tb = scan_bytes;
-        GMX_HIP(rocprim::inclusive_scan(scan_tmp.p, tb, deg.p, off.p + 1, (size_t) cur_count, rocprim::plus<int64_t>(), 0));
-        GMX_HIP(hipMemsetAsync(off.p, 0, sizeof(int64_t), 0));
-        GMX_HIP(hipMemcpyAsync(h_mf, off.p + cur_count, sizeof(int64_t), hipMemcpyDeviceToHost, 0));
-        GMX_HIP(hipStreamSynchronize(0));
-        const int64_t m_f = *h_mf;
-        const int64_t nb = (cur_count + m_f + BFS_ITEMS - 1) / BFS_ITEMS;
-        if (nb > 0) {
-            hipLaunchKernelGGL(bfs_merge_split_kernel, dim3((unsigned) ((nb + 1 + BFS_THREADS - 1) / BFS_THREADS)), dim3(BFS_THREADS), 0, 0,
-                               (const int64_t*) off.p, cur_count, m_f, nb, split.p);
-            hipLaunchKernelGGL(sssp_relax_kernel, dim3((unsigned) nb), dim3(BFS_THREADS), 0, 0, g->begin.p, g->node_idx.p,
-                               len_dev, cur_q, cur_count, off.p, m_f, round, dist.p, stamp.p, next_q, ctr.p, (const int64_t*) split.p);
-        }
-        GMX_HIP(hipGetLastError());
-        GMX_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof(bfs_counters), hipMemcpyDeviceToHost, 0));
-        GMX_HIP(hipStreamSynchronize(0));
-        const bfs_counters& h = *h_ctr;
-        unsigned long long found_unused = 0;
-        cur_count = (int64_t) h.next_count;
-        bfs_totals(h, &edges, &found_unused);
-        requeued += cur_count;
-        int32_t* t = cur_q;
-        cur_q = next_q;
-        next_q = t;
-        round++;
-    }
-    GMX_HIP(hipEventRecord(ev[1], 0));
-    GMX_HIP(hipEventSynchronize(ev[1]));
-    GMX_HIP(hipMemcpy(dist_host, dist.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    if (stats) {
-        float ms = 0, hms = 0;
-        (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-        (void) hipEventElapsedTime(&hms, ev[2], ev[3]);
-        stats->iterations = round;
-        stats->kernel_ms = ms;
-        stats->h2d_ms = hms;
-        stats->edges_examined = (int64_t) edges;
-        stats->vertices_reached = requeued + (root_ok ? 1 : 0);   // queue entries over all rounds (a vertex may re-enter)
-    }
-    return GMX_OK;
-}
-
-// ------------------------------------------------------------------ sssp_path: the shortest-path tree next to the lengths
-// The emitted `sssp_path` (/root/reference/apps/src/sssp_path.gm:1-30) is sssp's loop whose min= also records the winner:
-//     <s.dist_nxt; s.updated_nxt, s.prev> min= <n.dist + e.len; True, n>
-// Which of several equally short predecessors it records depends on the reference's thread timing.  The device returns a
-// fixed member of that set: distance and predecessor slot of a vertex are ONE 64-bit word,
-//     key[v] = (dist << 32) | device slot of the in-edge        (root: (0, NIL); unreached: (INT_MAX, NIL))
-// and relaxing slot e = n -> s offers (dist[n] + len[e], e) with one 64-bit unsigned atomicMin.  Ties in the distance are
-// offered too, so among the candidates at the final distance -- exactly the tight in-edges, each offered after its
-// source's last drop (a candidate that equals the final distance of s cannot come from a source above its own final
-// distance) -- the smallest slot wins whatever the order.  A zero-length edge may only win when it lowers the distance
-// strictly (compare-and-swap): the vertices of a zero-length cycle then take their predecessors in the order in which
-// they reached the distance, which has no cycle.  Lengths must be >= 0 (the word orders distances as unsigned).
-// The schedule has to keep one invariant: every vertex relaxes all its out-edges at least once after its last drop,
-// reading its current distance.  Two schedules do:
-//   round queue   gmx_sssp's: a vertex whose distance dropped in round r is relaxed in round r + 1;
-//   near / far    a drop below the threshold T goes to the next round's queue, the others to a far pile; when the queue
-//                 runs dry T advances by delta (further, when nothing lies below it) and the pile is filtered: entries
-//                 whose vertex is below the old T are stale (it was queued when it got there, and relaxed since), the
-//                 others go to the queue (below the new T) or stay, each vertex once.
-// stamp[v] = 2 * tag + (queued: 1, piled: 0) of the last time v entered either, tags rising from launch to launch.
-#define SP_NIL 0xFFFFFFFFu
-#define SP_WORD(d, e) (((unsigned long long) (uint32_t) (d) << 32) | (unsigned long long) (uint32_t) (e))
-// slots of bfs_counters::pad0 the far pile uses (same cache line as next_count: one claim per workgroup)
-#define SP_FAR_TAIL 0   // entries in the pile being written
-#define SP_FAR_NEAREST 1   // filter: max over the kept entries of (2^32 - distance); 0 = none kept
-#define SP_FAR_SPILL 2   // an entry did not fit (never, by the host's accounting): the call fails instead of writing
-
-__global__ void sp_init_kernel(unsigned long long* __restrict__ key, int32_t* __restrict__ stamp, int64_t V, int32_t root) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    for (; i < V; i += stride) {
-        key[i] = SP_WORD(i == root ? 0 : INT_MAX, SP_NIL);
-        stamp[i] = -1;
-    }
-}
-
-// out[0] = number of negative lengths, out[1] = sum of the lengths (one atomic per workgroup and value)
-__global__ void __launch_bounds__(BFS_THREADS)
-sp_len_check_kernel(const int32_t* __restrict__ len, int64_t E, unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long s_neg[BFS_THREADS / 64], s_sum[BFS_THREADS / 64];
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    unsigned long long neg = 0, sum = 0;
-    for (; i < E; i += stride) {
-        const int32_t l = len[i];
-        neg += l < 0;
-        sum += l < 0 ? 0ull : (unsigned long long) l;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        neg += __shfl_down(neg, o, 64);
-        sum += __shfl_down(sum, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_neg[threadIdx.x >> 6] = neg;
-        s_sum[threadIdx.x >> 6] = sum;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        neg = sum = 0;
-        for (int w = 0; w < BFS_THREADS / 64; w++) {
-            neg += s_neg[w];
-            sum += s_sum[w];
-        }
-        if (neg) atomicAdd(&out[0], neg);
-        if (sum) atomicAdd(&out[1], sum);
-    }
-}
-
-// the lanes of a wave that have a vertex for a workgroup's list append together
-__device__ __forceinline__ void sp_stage(bool on, int32_t v, int32_t* s_list, unsigned int* s_n, int lane) {
-    const unsigned long long mk = __ballot(on);
-    if (mk) {
-        const int leader = __ffsll((long long) mk) - 1;
-        unsigned int at = 0;
-        if (lane == leader) at = atomicAdd(s_n, (unsigned int) __popcll(mk));
-        at = __shfl(at, leader, 64);
-        if (on) s_list[at + __popcll(mk & ((1ULL << lane) - 1))] = v;
-    }
-}
-
-// sssp_relax_kernel's shape with the packed word.  NEARFAR: drops to threshold or above go to the far pile.
-template <bool NEARFAR>
-__global__ void __launch_bounds__(BFS_THREADS)
-sp_relax_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ node_idx, const int32_t* __restrict__ len,
-                const int32_t* __restrict__ cur_q, int64_t n, const int64_t* __restrict__ off, int64_t m, int32_t tag,
-                unsigned long long* key, int32_t* __restrict__ stamp, int32_t* __restrict__ next_q, int32_t* __restrict__ far_q,
-                unsigned long long far_cap, uint32_t threshold, bfs_counters* __restrict__ ctr, const int64_t* __restrict__ split) {
-    __shared__ int64_t s_off[BFS_ITEMS + 2];
-    __shared__ int32_t s_row[BFS_ITEMS + 2];
-    __shared__ uint32_t s_dist[BFS_ITEMS + 2];
-    __shared__ int32_t s_win[BFS_ITEMS];   // (one queue-tail claim per workgroup, as in sssp_relax_kernel)
-    __shared__ int32_t s_far[NEARFAR ? BFS_ITEMS : 1];
-    __shared__ unsigned int s_nwin, s_nfar;
-    __shared__ unsigned long long s_base, s_fbase;
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (tid == 0) s_nwin = s_nfar = 0;
-    int64_t d0 = (int64_t) blockIdx.x * BFS_ITEMS, d1 = d0 + BFS_ITEMS;
-    if (d1 > n + m) d1 = n + m;
-    const int64_t v0 = split[blockIdx.x], v1 = split[blockIdx.x + 1], e0 = d0 - v0, e1 = d1 - v1;
-    const int nv = (int) (v1 - v0) + 1;
-    for (int i = tid; i < nv; i += BFS_THREADS) {
-        const int64_t vi = v0 + i;
-        s_off[i] = vi <= n ? off[vi < n ? vi : n] : m;
-        const int32_t v = vi < n ? cur_q[vi] : 0;
-        s_row[i] = vi < n ? begin[v] : 0;
-        s_dist[i] = vi < n ? (uint32_t) (key[v] >> 32) : 0u;   // the current distance (a later drop queues v again)
-    }
-    if (tid == 0) s_off[nv] = m + 1;
-    __syncthreads();
-    unsigned long long inspected = 0;
-    for (int64_t x = e0 + tid; x < e1; x += BFS_THREADS) {
-        int lo = 0, hi = nv - 1;
-        while (lo < hi) {
-            int mid = (lo + hi + 1) >> 1;
-            if (s_off[mid] <= x) lo = mid; else hi = mid - 1;
-        }
-        const int64_t e = (int64_t) s_row[lo] + (x - s_off[lo]);
-        const int32_t s = node_idx[e];
-        const int32_t l = len[e];
-        const uint32_t nd = s_dist[lo] + (uint32_t) l;
-        const unsigned long long cand = SP_WORD(nd, e);
-        inspected++;
-        // <s.dist_nxt; s.updated_nxt, s.prev> min= <n.dist + e.len; True, n>   (sssp_path.gm:21)
-        unsigned long long cur = key[s];   // (a stale copy is only higher: the atomic decides)
-        bool dropped = false;
-        if (l > 0) {
-            if (cand < cur) dropped = (uint32_t) (atomicMin(&key[s], cand) >> 32) > nd;   // equal distance: a smaller slot, no new work
-        } else {
-            while ((uint32_t) (cur >> 32) > nd) {   // zero length: only a strictly lower distance
-                const unsigned long long seen = atomicCAS(&key[s], cur, cand);
-                if (seen == cur) {
-                    dropped = true;
-                    break;
-                }
-                cur = seen;
-            }
-        }
-        bool to_queue = false, to_pile = false;
-        if (dropped) {
-            const bool near = !NEARFAR || nd < threshold;
-            const int32_t mark = 2 * tag + (near ? 1 : 0);
-            const bool first = atomicMax(&stamp[s], mark) < mark;   // (piled and then queued in one launch: both)
-            to_queue = first && near;
-            to_pile = first && !near;
-        }
-        sp_stage(to_queue, s, s_win, &s_nwin, lane);
-        if (NEARFAR) sp_stage(to_pile, s, s_far, &s_nfar, lane);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) inspected += __shfl_down(inspected, o, 64);
-    if (lane == 0) bfs_count(ctr, inspected, 0);
-    __syncthreads();
-    const unsigned int nwin = s_nwin, nfar = NEARFAR ? s_nfar : 0u;
-    if (nwin == 0 && nfar == 0) return;   // (workgroup-uniform)
-    if (tid == 0) {
-        if (nwin) s_base = atomicAdd(&ctr->next_count, (unsigned long long) nwin);
-        if (nfar) s_fbase = atomicAdd(&ctr->pad0[SP_FAR_TAIL], (unsigned long long) nfar);
-    }
-    __syncthreads();
-    for (unsigned int i = tid; i < nwin; i += BFS_THREADS) next_q[s_base + i] = s_win[i];
-    if (NEARFAR && nfar) {
-        if (s_fbase + nfar <= far_cap) {
-            for (unsigned int i = tid; i < nfar; i += BFS_THREADS) far_q[s_fbase + i] = s_far[i];
-        } else if (tid == 0) {
-            ctr->pad0[SP_FAR_SPILL] = 1ull;
-        }
-    }
-}
-
-// The far pile when the threshold moves from t_old to t_new (or, with t_new == t_old, when the pile is only to be made
-// smaller): see the schedule above.  near_q takes at most one entry per vertex, far_out at most min(n, V).
-__global__ void __launch_bounds__(BFS_THREADS)
-sp_refilter_kernel(const int32_t* __restrict__ far_in, int64_t n, const unsigned long long* __restrict__ key, int32_t* __restrict__ stamp,
-                   int32_t tag, uint32_t t_old, uint32_t t_new, int32_t* __restrict__ near_q, int32_t* __restrict__ far_out,
-                   bfs_counters* __restrict__ ctr) {
-    __shared__ int32_t s_win[BFS_ITEMS];
-    __shared__ int32_t s_far[BFS_ITEMS];
-    __shared__ unsigned int s_nwin, s_nfar;
-    __shared__ unsigned long long s_base, s_fbase, s_nearest;
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (tid == 0) {
-        s_nwin = s_nfar = 0;
-        s_nearest = 0;
-    }
-    __syncthreads();
-    unsigned long long nearest = 0;
-    const int64_t i0 = (int64_t) blockIdx.x * BFS_ITEMS;
-    for (int k = 0; k < BFS_ITEMS / BFS_THREADS; k++) {   // (every lane runs every step: whole waves at the ballots)
-        const int64_t i = i0 + tid + (int64_t) k * BFS_THREADS;
-        bool to_queue = false, to_pile = false;
-        int32_t v = 0;
-        if (i < n) {
-            v = far_in[i];
-            const uint32_t d = (uint32_t) (key[v] >> 32);
-            if (d >= t_old) {
-                const bool near = d < t_new;
-                const int32_t mark = 2 * tag + (near ? 1 : 0);
-                const bool first = atomicMax(&stamp[v], mark) < mark;
-                to_queue = first && near;
-                to_pile = first && !near;
-                if (to_pile) {
-                    const unsigned long long inv = 0x100000000ull - (unsigned long long) d;
-                    nearest = inv > nearest ? inv : nearest;
-                }
-            }
-        }
-        sp_stage(to_queue, v, s_win, &s_nwin, lane);
-        sp_stage(to_pile, v, s_far, &s_nfar, lane);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_down(nearest, o, 64);
-        nearest = t > nearest ? t : nearest;
-    }
-    if (lane == 0 && nearest) atomicMax(&s_nearest, nearest);
-    __syncthreads();
-    const unsigned int nwin = s_nwin, nfar = s_nfar;
-    if (nwin == 0 && nfar == 0) return;   // (workgroup-uniform)
-    if (tid == 0) {
-        if (nwin) s_base = atomicAdd(&ctr->next_count, (unsigned long long) nwin);
-        if (nfar) {
-            s_fbase = atomicAdd(&ctr->pad0[SP_FAR_TAIL], (unsigned long long) nfar);
-            atomicMax(&ctr->pad0[SP_FAR_NEAREST], s_nearest);
-        }
-    }
-    __syncthreads();
-    for (unsigned int i = tid; i < nwin; i += BFS_THREADS) near_q[s_base + i] = s_win[i];
-    for (unsigned int i = tid; i < nfar; i += BFS_THREADS) far_out[s_fbase + i] = s_far[i];
-}
-
-// one thread per vertex splits the word: dist, the predecessor slot as an UPLOADED slot, and the row that holds it
-__global__ void sp_finish_kernel(const unsigned long long* __restrict__ key, const int32_t* __restrict__ begin,
-                                 const int32_t* __restrict__ e_idx2idx /* NULL: the device slots are the uploaded ones */, int64_t V,
-                                 int32_t* __restrict__ dist, int32_t* __restrict__ prev_node, int32_t* __restrict__ prev_edge) {
-    int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    for (; v < V; v += stride) {
-        const unsigned long long k = key[v];
-        const uint32_t e = (uint32_t) k;
-        dist[v] = (int32_t) (k >> 32);
-        int32_t pn = -1, pe = -1;
-        if (e != SP_NIL) {
-            int64_t lo = 0, hi = V - 1;   // the last row that starts at or before e (the empty rows before it start there too)
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if ((uint32_t) begin[mid] <= e) lo = mid; else hi = mid - 1;
-            }
-            pn = (int32_t) lo;
-            pe = e_idx2idx ? e_idx2idx[e] : (int32_t) e;
-        }
-        prev_node[v] = pn;
-        prev_edge[v] = pe;
-    }
-}
-
-// GMX_SSSP_PATH_SCHEDULE = round | nearfar (read at every call); GMX_SSSP_DELTA = the near / far threshold step
-static bool sp_use_nearfar() {
-    const char* s = getenv("GMX_SSSP_PATH_SCHEDULE");
-    if (s && !strcmp(s, "nearfar")) return true;
-    if (s && !strcmp(s, "round")) return false;
-    return false;
-}
-
-extern "C" int gmx_sssp_path(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host, int32_t* dist_host, gmx_node_t* prev_node_host,
-                             gmx_edge_t* prev_edge_host, gmx_stats_t* stats) {
-    GMX_REQUIRE(g && dist_host && prev_node_host, "NULL argument");
-    GMX_REQUIRE(len_host || g->E == 0, "len is NULL");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    const int64_t V = g->V, E = g->E;
-    if (V == 0) return GMX_OK;
-    const bool root_ok = root >= 0 && root < V;
-    const bool nearfar = sp_use_nearfar();
-    const size_t far_cap = nearfar ? 2 * (size_t) V : 0;   // a launch adds at most V entries to a pile of at most V
-    dbuf<unsigned long long> key, chk;
-    dbuf<int32_t> stamp, q0, q1, deg, len, far0, far1, out;
-    dbuf<int64_t> off, split;
-    dbuf<bfs_counters> ctr;
-    dbuf<char> scan_tmp;
-    size_t scan_bytes = 0;
-    GMX_CHECK(split.alloc((size_t) ((V + E) / BFS_ITEMS + 3)));
-    GMX_CHECK(key.alloc((size_t) V));
-    GMX_CHECK(chk.alloc(2));
-    GMX_CHECK(stamp.alloc((size_t) V));
-    GMX_CHECK(q0.alloc((size_t) V));
-    GMX_CHECK(q1.alloc((size_t) V));
-    GMX_CHECK(deg.alloc((size_t) V));
-    GMX_CHECK(off.alloc((size_t) V + 2));
-    GMX_CHECK(ctr.alloc(1));
-    GMX_CHECK(len.alloc((size_t) (E ? E : 1)));
-    GMX_CHECK(out.alloc(3 * (size_t) V));
-    if (nearfar) {
-        GMX_CHECK(far0.alloc(far_cap));
-        GMX_CHECK(far1.alloc(far_cap));
-    }
-    GMX_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, deg.p, off.p + 1, (size_t) V, rocprim::plus<int64_t>(), 0));
-    GMX_CHECK(scan_tmp.alloc(scan_bytes));
-    ev_guard evg[6];
-    hipEvent_t ev[6];
-    for (int i = 0; i < 6; i++) {
-        GMX_CHECK(evg[i].create());
-        ev[i] = evg[i].e;
-    }
-    pinned_guard<bfs_counters> pg_ctr;
-    pinned_guard<int64_t> pg_mf;
-    GMX_CHECK(pg_ctr.alloc());
-    GMX_CHECK(pg_mf.alloc());
-    bfs_counters* h_ctr = pg_ctr.p;
-    int64_t* h_mf = pg_mf.p;
-    // the property: copied in, checked on the device copy (negative lengths are refused), brought into the order of the
-    // sorted rows when the upload sorted them
-    GMX_HIP(hipEventRecord(ev[2], 0));
-    unsigned long long h_chk[2] = {0, 0};
-    if (E) {
-        GMX_HIP(hipMemcpy(len.p, len_host, sizeof(int32_t) * (size_t) E, hipMemcpyHostToDevice));
-        GMX_HIP(hipMemsetAsync(chk.p, 0, 2 * sizeof(unsigned long long), 0));
-        hipLaunchKernelGGL(sp_len_check_kernel, dim3(grid_for(E)), dim3(BFS_THREADS), 0, 0, (const int32_t*) len.p, E, chk.p);
-        GMX_HIP(hipGetLastError());
-        GMX_HIP(hipMemcpy(h_chk, chk.p, sizeof(h_chk), hipMemcpyDeviceToHost));
-        GMX_REQUIRE(h_chk[0] == 0, "len holds %llu negative value(s): gmx_sssp_path needs len >= 0", h_chk[0]);
-    }
-    dbuf<int32_t> len_sorted;
-    if (E && g->e_idx2idx.p) {
-        GMX_CHECK(len_sorted.alloc((size_t) E));
-        hipLaunchKernelGGL(gather_by_order_kernel, dim3(grid_for(E)), dim3(BFS_THREADS), 0, 0, (const int32_t*) len.p,
-                           (const int32_t*) g->e_idx2idx.p, E, len_sorted.p);
-    }
-    const int32_t* len_dev = len_sorted.p ? len_sorted.p : len.p;
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    // near / far: delta = 32 * mean length / mean out-degree (a queue round then holds about a wave's worth of edges per
-    // vertex of the band), at least 1
-    uint32_t delta = 1;
-    if (nearfar) {
-        double dl = E ? 32.0 * ((double) h_chk[1] / (double) E) / ((double) E / (double) V) : 1.0;
-        const char* s = getenv("GMX_SSSP_DELTA");
-        if (s && atof(s) >= 1.0) dl = atof(s);
-        delta = dl < 1.0 ? 1u : dl > 1073741824.0 ? (1u << 30) : (uint32_t) dl;
-    }
-    const uint32_t T_ALL = 0x80000000u;   // above every distance
-    uint32_t T = nearfar ? delta : T_ALL;
-    GMX_HIP(hipEventRecord(ev[0], 0));
-    hipLaunchKernelGGL(sp_init_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, key.p, stamp.p, V, root_ok ? root : -1);
-    int64_t cur_count = 0, queued = 0, far_n = 0;
-    unsigned long long edges = 0;
-    int32_t rounds = 0, tag = 0;
-    int32_t* cur_q = q0.p;
-    int32_t* next_q = q1.p;
-    int32_t* far_cur = far0.p;
-    int32_t* far_alt = far1.p;
-    if (root_ok) {
-        GMX_HIP(hipMemcpy(q0.p, &root, sizeof(int32_t), hipMemcpyHostToDevice));
-        cur_count = queued = 1;
-    }
-    GMX_HIP(hipMemsetAsync(ctr.p, 0, sizeof(bfs_counters), 0));
-    // filter the pile far_cur[0 .. far_n) into cur_q (which is empty, or untouched when t_new == t_old) and far_alt
-    auto refilter = [&](uint32_t t_old, uint32_t t_new, int64_t* near_n, uint32_t* nearest) -> int {
-        GMX_HIP(hipMemsetAsync(&ctr.p->next_count, 0, (2 + SP_FAR_NEAREST + 1) * sizeof(unsigned long long), 0));
-        hipLaunchKernelGGL(sp_refilter_kernel, dim3((unsigned) ((far_n + BFS_ITEMS - 1) / BFS_ITEMS)), dim3(BFS_THREADS), 0, 0,
-                           (const int32_t*) far_cur, far_n, (const unsigned long long*) key.p, stamp.p, tag, t_old, t_new, cur_q, far_alt, ctr.p);
-        GMX_HIP(hipGetLastError());
-        GMX_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof(bfs_counters), hipMemcpyDeviceToHost, 0));
-        GMX_HIP(hipStreamSynchronize(0));
-        tag++;
-        *near_n = (int64_t) h_ctr->next_count;
-        far_n = (int64_t) h_ctr->pad0[SP_FAR_TAIL];
-        *nearest = h_ctr->pad0[SP_FAR_NEAREST] ? (uint32_t) (0x100000000ull - h_ctr->pad0[SP_FAR_NEAREST]) : 0u;
-        int32_t* t = far_cur;
-        far_cur = far_alt;
-        far_alt = t;
-        return GMX_OK;
-    };
-    for (;;) {
-        while (cur_count > 0) {
-            if (nearfar && far_n > V) {   // room for this round's (at most V) new entries: drop the stale ones and the repeats
-                int64_t none = 0;
-                uint32_t unused = 0;
-                GMX_CHECK(refilter(T, T, &none, &unused));
-                GMX_REQUIRE(none == 0 && far_n <= V, "gmx_sssp_path: far pile accounting");
-            }
-            GMX_HIP(hipMemsetAsync(&ctr.p->next_count, 0, sizeof(unsigned long long), 0));   // (`edges` and the pile's tail run on)
-            hipLaunchKernelGGL(bfs_degree_kernel, dim3(grid_for(cur_count)), dim3(BFS_THREADS), 0, 0, g->begin.p, cur_q, cur_count, deg.p);
-            size_t tb = scan_bytes;
-            GMX_HIP(rocprim::inclusive_scan(scan_tmp.p, tb, deg.p, off.p + 1, (size_t) cur_count, rocprim::plus<int64_t>(), 0));
-            GMX_HIP(hipMemsetAsync(off.p, 0, sizeof(int64_t), 0));
-            GMX_HIP(hipMemcpyAsync(h_mf, off.p + cur_count, sizeof(int64_t), hipMemcpyDeviceToHost, 0));
-            GMX_HIP(hipStreamSynchronize(0));
-            const int64_t m_f = *h_mf;
-            const int64_t nb = (cur_count + m_f + BFS_ITEMS - 1) / BFS_ITEMS;
-            if (nb > 0) {
-                hipLaunchKernelGGL(bfs_merge_split_kernel, dim3((unsigned) ((nb + 1 + BFS_THREADS - 1) / BFS_THREADS)), dim3(BFS_THREADS), 0, 0,
-                                   (const int64_t*) off.p, cur_count, m_f, nb, split.p);
-                if (nearfar)
-                    hipLaunchKernelGGL(sp_relax_kernel<true>, dim3((unsigned) nb), dim3(BFS_THREADS), 0, 0, g->begin.p, g->node_idx.p, len_dev,
-                                       cur_q, cur_count, off.p, m_f, tag, key.p, stamp.p, next_q, far_cur, (unsigned long long) far_cap, T,
-                                       ctr.p, (const int64_t*) split.p);
-                else
-                    hipLaunchKernelGGL(sp_relax_kernel<false>, dim3((unsigned) nb), dim3(BFS_THREADS), 0, 0, g->begin.p, g->node_idx.p, len_dev,
-                                       cur_q, cur_count, off.p, m_f, tag, key.p, stamp.p, next_q, (int32_t*) nullptr, 0ull, T, ctr.p,
-                                       (const int64_t*) split.p);
-            }
-            GMX_HIP(hipGetLastError());
-            GMX_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof(bfs_counters), hipMemcpyDeviceToHost, 0));
-            GMX_HIP(hipStreamSynchronize(0));
-            const bfs_counters& h = *h_ctr;
-            unsigned long long found_unused = 0;
-            cur_count = (int64_t) h.next_count;
-            far_n = (int64_t) h.pad0[SP_FAR_TAIL];
-            GMX_REQUIRE(h.pad0[SP_FAR_SPILL] == 0 && far_n <= (int64_t) far_cap, "gmx_sssp_path: far pile overflow");
-            bfs_totals(h, &edges, &found_unused);
-            queued += cur_count;
-            int32_t* t = cur_q;
-            cur_q = next_q;
-            next_q = t;
-            rounds++;
-            tag++;
-        }
-        if (far_n == 0) break;
-        // the queue ran dry: advance the threshold; when nothing lies below the new one, to just above the nearest entry
-        uint32_t nearest = 0;
-        const uint32_t t_old = T;
-        T = T > T_ALL - delta ? T_ALL : T + delta;
-        GMX_CHECK(refilter(t_old, T, &cur_count, &nearest));
-        if (cur_count == 0 && far_n > 0) {
-            const uint64_t up = ((uint64_t) nearest / delta + 1) * (uint64_t) delta;
-            const uint32_t t_prev = T;
-            T = up > T_ALL ? T_ALL : (uint32_t) up;
-            GMX_CHECK(refilter(t_prev, T, &cur_count, &nearest));
-            GMX_REQUIRE(cur_count > 0, "gmx_sssp_path: threshold accounting");
-        }
-        queued += cur_count;
-    }
-    hipLaunchKernelGGL(sp_finish_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, (const unsigned long long*) key.p, (const int32_t*) g->begin.p,
-                       (const int32_t*) g->e_idx2idx.p, V, out.p, out.p + V, out.p + 2 * V);
-    GMX_HIP(hipGetLastError());
-    GMX_HIP(hipEventRecord(ev[1], 0));
-    GMX_HIP(hipEventSynchronize(ev[1]));
-    GMX_HIP(hipEventRecord(ev[4], 0));
-    GMX_HIP(hipMemcpy(dist_host, out.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    GMX_HIP(hipMemcpy(prev_node_host, out.p + V, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    if (prev_edge_host) GMX_HIP(hipMemcpy(prev_edge_host, out.p + 2 * V, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[5], 0));
-    GMX_HIP(hipEventSynchronize(ev[5]));
-    if (stats) {
-        float ms = 0, hms = 0, dms = 0;
-        (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-        (void) hipEventElapsedTime(&hms, ev[2], ev[3]);
-        (void) hipEventElapsedTime(&dms, ev[4], ev[5]);
-        stats->iterations = rounds;
-        stats->kernel_ms = ms;
-        stats->h2d_ms = hms;
-        stats->d2h_ms = dms;
-        stats->edges_examined = (int64_t) edges;
-        stats->vertices_reached = queued;   // queue entries over all rounds (a vertex may re-enter), the root's included
-    }
-    return GMX_OK;
-}
 
 // ------------------------------------------------------------------ BFS object: InBFS / InReverse
 // The device counterpart of gm_bfs_template<level_t = short, ..., save_child> (gm_bfs_template.h:14-312) as the
@@ -2288,10 +1503,10 @@ extern "C" int gmx_bc(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, i
     GMX_HIP(hipMemsetAsync(sd.p, 0, sizeof(float2) * (size_t) V, 0));   // (delta of a vertex no visit has written is never read; zero all the same)
     GMX_CHECK(bc.alloc((size_t) V));
     bfs_order ord;
-    ev_guard e0, e1;
+    gmx_event e0, e1;
     GMX_CHECK(e0.create());
     GMX_CHECK(e1.create());
-    GMX_HIP(hipEventRecord(e0.e, 0));
+    GMX_HIP(hipEventRecord(e0, 0));
     hipLaunchKernelGGL(fill_f32_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, bc.p, V, 0.0f, (int64_t) -1, 0.0f);   // G.BC = 0
     int64_t reached = 0;
     for (int32_t si = 0; si < nseeds; si++) {   // For (s: Seeds.Items): sequential, as emitted
@@ -2303,12 +1518,12 @@ extern "C" int gmx_bc(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, i
         const int32_t skip = skip_root ? s : -1;
         GMX_CHECK(bfs_sweep(g, b, ord, skip, bc_visit_fw{sd.p}, bc_visit_rv{sd.p, bc.p}, big_list.p, big_count.p));
     }
-    GMX_HIP(hipEventRecord(e1.e, 0));
-    GMX_HIP(hipEventSynchronize(e1.e));
+    GMX_HIP(hipEventRecord(e1, 0));
+    GMX_HIP(hipEventSynchronize(e1));
     GMX_HIP(hipMemcpy(bc_host, bc.p, sizeof(float) * (size_t) V, hipMemcpyDeviceToHost));
     if (stats) {
         float ms = 0;
-        (void) hipEventElapsedTime(&ms, e0.e, e1.e);
+        (void) hipEventElapsedTime(&ms, e0, e1);
         stats->iterations = nseeds;
         stats->kernel_ms = ms;
         stats->vertices_reached = reached;
@@ -2342,492 +1557,6 @@ extern "C" int gmx_bfs_levels(gmx_graph_t* g, gmx_node_t root, int16_t* level_ho
     return GMX_OK;
 }
 
-// ------------------------------------------------------------------ avg_teen_cnt, conduct
-// Count-reductions over neighbours with an integer node property (/root/reference/apps/src/avg_teen_cnt.gm,
-// conduct.gm).  Both are "expand the out-edges of the vertices that pass a filter and do something per edge":
-// the selected vertices are queued (ballot-aggregated append), their out-degrees prefix-summed and the edges
-// cut by merge-path as in a top-down BFS level.  Integer arithmetic only; the final float is formed on the
-// host from the exact integers with the emitted expression, so results are bit-identical.
-//   MODE 0: cnt[dst] += 1                     (teen_cnt[n] = #in-neighbours passing the filter)
-//   MODE 1: total += (prop[dst] != num)       (conduct's Cross)
-template <int MODE>
-__global__ void __launch_bounds__(BFS_THREADS)
-edge_count_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ node_idx,
-                  const int32_t* __restrict__ cur_q, int64_t n, const int64_t* __restrict__ off, int64_t m,
-                  const int32_t* __restrict__ prop, int32_t num, int32_t* __restrict__ cnt,
-                  unsigned long long* __restrict__ total) {
-    __shared__ int64_t s_off[BFS_ITEMS + 2];
-    __shared__ int32_t s_row[BFS_ITEMS + 2];
-    __shared__ int64_t s_split[2][2];
-    const int tid = threadIdx.x;
-    if (tid < 2) {
-        int64_t dk = ((int64_t) blockIdx.x + tid) * BFS_ITEMS;
-        if (dk > n + m) dk = n + m;
-        int64_t lo = dk > m ? dk - m : 0, hi = dk < n ? dk : n;
-        while (lo < hi) {
-            int64_t mid = (lo + hi) >> 1;
-            if (off[mid + 1] <= dk - mid - 1) lo = mid + 1; else hi = mid;
-        }
-        s_split[tid][0] = lo;
-        s_split[tid][1] = dk - lo;
-    }
-    __syncthreads();
-    const int64_t v0 = s_split[0][0], e0 = s_split[0][1], v1 = s_split[1][0], e1 = s_split[1][1];
-    const int nv = (int) (v1 - v0) + 1;
-    for (int i = tid; i < nv; i += BFS_THREADS) {
-        const int64_t vi = v0 + i;
-        s_off[i] = vi <= n ? off[vi < n ? vi : n] : m;
-        s_row[i] = vi < n ? begin[cur_q[vi]] : 0;
-    }
-    if (tid == 0) s_off[nv] = m + 1;
-    __syncthreads();
-    unsigned long long acc = 0;
-    for (int64_t x = e0 + tid; x < e1; x += BFS_THREADS) {
-        int lo = 0, hi = nv - 1;
-        while (lo < hi) {
-            int mid = (lo + hi + 1) >> 1;
-            if (s_off[mid] <= x) lo = mid; else hi = mid - 1;
-        }
-        const int32_t s = node_idx[(int64_t) s_row[lo] + (x - s_off[lo])];
-        if (MODE == 0) atomicAdd(&cnt[s], 1);
-        else acc += prop[s] != num ? 1 : 0;
-    }
-    if (MODE == 1) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-        if ((tid & 63) == 0 && acc) atomicAdd(total, acc);
-    }
-}
-
-// filter: 0: 10 <= prop < 20 (teen), 1: prop == num
-__global__ void select_queue_kernel(const int32_t* __restrict__ prop, int64_t V, int filter, int32_t num,
-                                    int32_t* __restrict__ q, unsigned long long* __restrict__ qcount) {
-    int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    const int64_t vend = (V + 63) / 64 * 64;
-    for (; v < vend; v += stride) {
-        bool in = false;
-        if (v < V) {
-            const int32_t p = prop[v];
-            in = filter == 0 ? (p >= 10 && p < 20) : (p == num);
-        }
-        const unsigned long long mk = __ballot(in);
-        if (mk) {
-            const int lane = threadIdx.x & 63;
-            const int leader = __ffsll((long long) mk) - 1;
-            unsigned long long base = 0;
-            if (lane == leader) base = atomicAdd(qcount, (unsigned long long) __popcll(mk));
-            base = __shfl(base, leader, 64);
-            if (in) q[base + __popcll(mk & ((1ULL << lane) - 1))] = (int32_t) v;
-        }
-    }
-}
-
-// out[0] += sum of val[v] (or of the out-degree) over the vertices passing the test, out[1] += their number
-//   test 0: prop[v] > num   test 1: prop[v] == num   test 2: prop[v] != num
-__global__ void filtered_sum_kernel(const int32_t* __restrict__ prop, const int32_t* __restrict__ val, const int32_t* __restrict__ begin,
-                                    int64_t V, int test, int32_t num, unsigned long long* __restrict__ out) {
-    int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    unsigned long long s = 0, c = 0;
-    for (; v < V; v += stride) {
-        const int32_t p = prop[v];
-        const bool ok = test == 0 ? p > num : test == 1 ? p == num : p != num;
-        if (ok) {
-            s += (unsigned long long) (long long) (val ? val[v] : begin[v + 1] - begin[v]);
-            c++;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_down(s, o, 64);
-        c += __shfl_down(c, o, 64);
-    }
-    // one pair of adds per workgroup (a pair per wave, all on one cache line, was 225 us of adds for a 20 us pass)
-    __shared__ unsigned long long s_s[BFS_THREADS / 64], s_c[BFS_THREADS / 64];
-    if ((threadIdx.x & 63) == 0) {
-        s_s[threadIdx.x >> 6] = s;
-        s_c[threadIdx.x >> 6] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long ts = 0, tc = 0;
-        for (int i = 0; i < (int) (blockDim.x >> 6); i++) {
-            ts += s_s[i];
-            tc += s_c[i];
-        }
-        if (ts) atomicAdd(&out[0], ts);
-        if (tc) atomicAdd(&out[1], tc);
-    }
-}
-
-// queue the vertices passing `filter`, then run edge_count_kernel<MODE> over their out-edges
-template <int MODE>
-static int expand_selected(gmx_graph* g, const int32_t* prop, int filter, int32_t num, int32_t* cnt, unsigned long long* total) {
-    const int64_t V = g->V;
-    dbuf<int32_t> q, deg;
-    dbuf<int64_t> off;
-    dbuf<unsigned long long> qcount;
-    dbuf<char> scan_tmp;
-    size_t scan_bytes = 0;
-    GMX_CHECK(q.alloc((size_t) V));
-    GMX_CHECK(deg.alloc((size_t) V));
-    GMX_CHECK(off.alloc((size_t) V + 2));
-    GMX_CHECK(qcount.alloc(1));
-    GMX_HIP(hipMemset(qcount.p, 0, sizeof(unsigned long long)));
-    hipLaunchKernelGGL(select_queue_kernel, dim3(grid_for(V, BFS_THREADS, 256 * 16)), dim3(BFS_THREADS), 0, 0, prop, V, filter, num, q.p, qcount.p);
-    unsigned long long nq = 0;
-    GMX_HIP(hipMemcpy(&nq, qcount.p, sizeof(nq), hipMemcpyDeviceToHost));
-    if (nq == 0) return GMX_OK;
-    hipLaunchKernelGGL(bfs_degree_kernel, dim3(grid_for((int64_t) nq)), dim3(BFS_THREADS), 0, 0, g->begin.p, q.p, (int64_t) nq, deg.p);
-    GMX_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, deg.p, off.p + 1, (size_t) nq, rocprim::plus<int64_t>(), 0));
-    GMX_CHECK(scan_tmp.alloc(scan_bytes));
-    GMX_HIP(rocprim::inclusive_scan(scan_tmp.p, scan_bytes, deg.p, off.p + 1, (size_t) nq, rocprim::plus<int64_t>(), 0));
-    GMX_HIP(hipMemsetAsync(off.p, 0, sizeof(int64_t), 0));
-    int64_t m_f = 0;
-    GMX_HIP(hipMemcpy(&m_f, off.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost));
-    const int64_t nb = ((int64_t) nq + m_f + BFS_ITEMS - 1) / BFS_ITEMS;
-    if (nb > 0)
-        hipLaunchKernelGGL(edge_count_kernel<MODE>, dim3((unsigned) nb), dim3(BFS_THREADS), 0, 0, g->begin.p, g->node_idx.p,
-                           (const int32_t*) q.p, (int64_t) nq, (const int64_t*) off.p, m_f, prop, num, cnt, total);
-    GMX_HIP(hipGetLastError());
-    return GMX_OK;
-}
-
-// Pull formulation with the predicate as a bitmap (V/8 bytes: resident in every L2): a row walks its neighbour
-// list and probes the bitmap -- no atomics, no gathers from a V-sized array.  Rows longer than ROWCNT_LONG are
-// left to whole waves.  mode bits: 1 = count the neighbours whose bit is CLEAR (else set); rows are taken only
-// if their own bit in `row_bm` is set (row_bm == NULL: all rows).  Per-row counts go to cnt (if given), their
-// sum to total (if given).
-#define ROWCNT_LONG 256
-__global__ void pred_bitmap_kernel(const int32_t* __restrict__ prop, int64_t V, int filter, int32_t num, unsigned long long* __restrict__ bm64) {
-    int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    const int64_t vend = (V + 63) / 64 * 64;
-    for (; v < vend; v += stride) {
-        bool in = false;
-        if (v < V) {
-            const int32_t p = prop[v];
-            in = filter == 0 ? (p >= 10 && p < 20) : (p == num);
-        }
-        const unsigned long long m = __ballot(in);
-        if ((threadIdx.x & 63) == 0) bm64[v >> 6] = m;
-    }
-}
-
-__global__ void __launch_bounds__(BFS_THREADS)
-row_count_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ idx, int64_t V,
-                 const uint32_t* __restrict__ row_bm, const uint32_t* __restrict__ probe_bm, int invert,
-                 int32_t* __restrict__ cnt, int32_t* __restrict__ long_rows, unsigned long long* __restrict__ nlong,
-                 unsigned long long* __restrict__ total) {
-    int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    unsigned long long acc = 0;
-    for (; v < V; v += stride) {
-        if (row_bm && !((row_bm[v >> 5] >> (v & 31)) & 1u)) {
-            if (cnt) cnt[v] = 0;
-            continue;
-        }
-        const int32_t b = begin[v], e = begin[v + 1];
-        if (e - b > ROWCNT_LONG) {
-            long_rows[atomicAdd(nlong, 1ULL)] = (int32_t) v;
-            continue;
-        }
-        int32_t c = 0;
-        for (int32_t i = b; i < e; i++) {
-            const int32_t w = idx[i];
-            const unsigned bit = (probe_bm[w >> 5] >> (w & 31)) & 1u;
-            c += invert ? (int32_t) (bit ^ 1u) : (int32_t) bit;
-        }
-        if (cnt) cnt[v] = c;
-        acc += (unsigned long long) c;
-    }
-    if (total) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-        if ((threadIdx.x & 63) == 0 && acc) atomicAdd(total, acc);
-    }
-}
-
-__global__ void __launch_bounds__(BFS_THREADS)
-row_count_long_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ idx, const int32_t* __restrict__ long_rows,
-                      unsigned long long nlong, const uint32_t* __restrict__ probe_bm, int invert,
-                      int32_t* __restrict__ cnt, unsigned long long* __restrict__ total) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long wave = ((unsigned long long) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const unsigned long long nwaves = ((unsigned long long) gridDim.x * blockDim.x) >> 6;
-    unsigned long long acc = 0;
-    for (; wave < nlong; wave += nwaves) {
-        const int32_t v = long_rows[wave];
-        const int32_t b = begin[v], e = begin[v + 1];
-        unsigned long long c = 0;
-        for (int32_t i = b + lane; i < e; i += 64) {
-            const int32_t w = idx[i];
-            const unsigned bit = (probe_bm[w >> 5] >> (w & 31)) & 1u;
-            c += invert ? (bit ^ 1u) : bit;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-        if (lane == 0) {
-            if (cnt) cnt[v] = (int32_t) c;
-            acc += c;
-        }
-    }
-    if (total && lane == 0 && acc) atomicAdd(total, acc);
-}
-
-// The same count over the FLAT slot array (round 3): a workgroup takes ROWCNT_ITEMS consecutive items of the merged sequence
-// (row ends, slots) -- merge-path over begin[], as in the top-down BFS level -- so that the slots are read coalesced, eight per
-// thread and all in flight, whatever the rows look like; a slot finds its row by bisection in the LDS copy of the range's
-// begin[] and adds its bit to the row's LDS counter.  With one row per lane (above) every lane walked its own list: 4-byte
-// loads, one 64-byte request each -- RMAT-24: avg_teen_cnt 6.1 ms, conduct 5.0 ms for 1 GB of slots.
-#define ROWCNT_ITEMS 2048
-// rows consumed at the diagonals k * ROWCNT_ITEMS, k = 0 .. nb: one thread per diagonal.  (Searched by the workgroups
-// themselves -- two threads, 24 dependent loads over begin[], everybody else at the barrier -- this was 19 of the ~27 us a
-// workgroup took.)
-__global__ void row_count_split_kernel(const int32_t* __restrict__ begin, int64_t V, int64_t E, int64_t nb, int64_t* __restrict__ split) {
-    const int64_t k = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (k > nb) return;
-    int64_t dk = k * ROWCNT_ITEMS;
-    if (dk > V + E) dk = V + E;
-    int64_t lo = dk > E ? dk - E : 0, hi = dk < V ? dk : V;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t) begin[mid + 1] <= dk - mid - 1) lo = mid + 1; else hi = mid;
-    }
-    split[k] = lo;
-}
-
-__global__ void __launch_bounds__(BFS_THREADS)
-row_count_flat_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ idx, int64_t V, int64_t E, const int64_t* __restrict__ split,
-                      const uint32_t* __restrict__ row_bm, const uint32_t* __restrict__ probe_bm, int invert,
-                      int32_t* __restrict__ cnt /* zeroed */, unsigned long long* __restrict__ total) {
-    __shared__ int32_t s_off[ROWCNT_ITEMS + 2];
-    __shared__ int32_t s_cnt[ROWCNT_ITEMS + 2];
-    const int tid = threadIdx.x;
-    // merge-path split of the diagonals k * ITEMS and (k + 1) * ITEMS: (rows consumed, slots consumed)
-    int64_t d0 = (int64_t) blockIdx.x * ROWCNT_ITEMS, d1 = d0 + ROWCNT_ITEMS;
-    if (d1 > V + E) d1 = V + E;
-    const int64_t v0 = split[blockIdx.x], v1 = split[blockIdx.x + 1], e0 = d0 - v0, e1 = d1 - v1;
-    const int nv = (int) (v1 - v0) + 1;   // rows touched: v0 .. v1 (the last one may be partial, or == V)
-    for (int i = tid; i < nv; i += BFS_THREADS) {
-        const int64_t vi = v0 + i;
-        s_off[i] = vi <= V ? begin[vi < V ? vi : V] : (int32_t) E;
-        // (the row's own bit, asked once per row, rides in the counter's sign: -1 = this row counts nothing)
-        s_cnt[i] = row_bm && vi < V && !((row_bm[vi >> 5] >> (vi & 31)) & 1u) ? -1 : 0;
-    }
-    if (tid == 0) s_off[nv] = INT_MAX;   // sentinel
-    __syncthreads();
-    if (e1 > e0) {   // (workgroup-uniform)
-        constexpr int K = ROWCNT_ITEMS / BFS_THREADS;
-        const int lane = tid & 63;
-        int32_t w[K], row[K];
-        bool on[K];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const int64_t x = e0 + tid + (int64_t) k * BFS_THREADS;
-            on[k] = x < e1;
-            const int64_t xc = on[k] ? x : e0;
-            int lo = 0, hi = nv - 1;     // row of slot x: last i with s_off[i] <= x
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if ((int64_t) s_off[mid] <= xc) lo = mid; else hi = mid - 1;
-            }
-            row[k] = lo;
-            on[k] = on[k] && s_cnt[lo] >= 0;   // (nobody adds to a row that counts nothing, so the sign stays)
-        }
-#pragma unroll
-        for (int k = 0; k < K; k++) w[k] = on[k] ? idx[e0 + tid + (int64_t) k * BFS_THREADS] : 0;   // (unasked rows' slots are not read)
-        uint32_t pw[K];
-#pragma unroll
-        for (int k = 0; k < K; k++) pw[k] = probe_bm[w[k] >> 5];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            // consecutive lanes hold consecutive slots: the lanes of one row are a run, and the run's first lane adds the
-            // run's count -- one LDS add per (row, wave, pass) instead of one per slot on the same word
-            const bool bit = on[k] && ((((pw[k] >> (w[k] & 31)) & 1u) != 0) != (invert != 0));
-            const unsigned long long m = __ballot(bit);
-            const int prev = __shfl_up(row[k], 1, 64);
-            const unsigned long long heads = __ballot(lane == 0 || prev != row[k]);
-            if (m && ((heads >> lane) & 1ull)) {
-                const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-                const int len = after ? __ffsll((long long) after) : 64 - lane;   // lanes of this run
-                const unsigned long long mask = (len == 64 ? ~0ull : ((1ull << len) - 1ull)) << lane;
-                const int c = __popcll(m & mask);
-                if (c) atomicAdd(&s_cnt[row[k]], c);
-            }
-        }
-    }
-    __syncthreads();
-    unsigned long long acc = 0;
-    for (int i = tid; i < nv; i += BFS_THREADS) {
-        const int32_t c = s_cnt[i];
-        if (c <= 0) continue;
-        acc += (unsigned long long) c;
-        if (cnt) {
-            const int64_t r = v0 + i;
-            // a row whose slots all lie in this workgroup's range is written; the (at most two) rows cut by the range add
-            const bool whole = (int64_t) s_off[i] >= e0 && i + 1 < nv && (int64_t) s_off[i + 1] <= e1;
-            if (whole) cnt[r] = c; else atomicAdd(&cnt[r], c);
-        }
-    }
-    if (total) {   // one add per workgroup, on one of 64 words (131 K workgroups adding to ONE word: ~90 adds per us, 3.7 ms)
-        __shared__ unsigned long long s_red[BFS_THREADS / 64];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-        if ((tid & 63) == 0) s_red[tid >> 6] = acc;
-        __syncthreads();
-        if (tid == 0) {
-            unsigned long long t = 0;
-            for (int i = 0; i < BFS_THREADS / 64; i++) t += s_red[i];
-            if (t) atomicAdd(&total[blockIdx.x & 63], t);
-        }
-    }
-}
-__global__ void sum_shards_kernel(const unsigned long long* __restrict__ shard, unsigned long long* __restrict__ total) {
-    unsigned long long t = shard[threadIdx.x];   // 64 threads
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
-    if (threadIdx.x == 0 && t) atomicAdd(total, t);
-}
-
-// rows (all, or those whose bit is set in row_bm) count their neighbours by the probe bitmap; cnt (if given) is zeroed by the caller
-static int count_by_bitmap(const int32_t* begin, const int32_t* idx, int64_t V, int64_t E, const unsigned long long* row_bm,
-                           const unsigned long long* probe_bm, int invert, int32_t* cnt, unsigned long long* total) {
-    if (getenv("GMX_ROWCNT_PER_ROW")) {   // development option: the one-row-per-lane form
-        dbuf<int32_t> long_rows;
-        dbuf<unsigned long long> nlong;
-        GMX_CHECK(long_rows.alloc((size_t) V));
-        GMX_CHECK(nlong.alloc(1));
-        GMX_HIP(hipMemsetAsync(nlong.p, 0, sizeof(unsigned long long), 0));
-        hipLaunchKernelGGL(row_count_kernel, dim3(grid_for(V, BFS_THREADS, 256 * 32)), dim3(BFS_THREADS), 0, 0, begin, idx, V,
-                           (const uint32_t*) row_bm, (const uint32_t*) probe_bm, invert, cnt, long_rows.p, nlong.p, total);
-        unsigned long long h = 0;
-        GMX_HIP(hipMemcpy(&h, nlong.p, sizeof(h), hipMemcpyDeviceToHost));
-        if (h) {
-            int64_t wb = (int64_t) ((h * 64 + BFS_THREADS - 1) / BFS_THREADS);
-            if (wb > 256 * 32) wb = 256 * 32;
-            hipLaunchKernelGGL(row_count_long_kernel, dim3((unsigned) wb), dim3(BFS_THREADS), 0, 0, begin, idx, (const int32_t*) long_rows.p, h,
-                               (const uint32_t*) probe_bm, invert, cnt, total);
-        }
-        GMX_HIP(hipGetLastError());
-        return GMX_OK;
-    }
-    const int64_t nb = (V + E + ROWCNT_ITEMS - 1) / ROWCNT_ITEMS;
-    if (nb > 0) {
-        dbuf<int64_t> split;
-        dbuf<unsigned long long> shard;
-        GMX_CHECK(split.alloc((size_t) nb + 1));
-        GMX_CHECK(shard.alloc(64));
-        GMX_HIP(hipMemsetAsync(shard.p, 0, 64 * sizeof(unsigned long long), 0));
-        hipLaunchKernelGGL(row_count_split_kernel, dim3((unsigned) ((nb + 1 + BFS_THREADS - 1) / BFS_THREADS)), dim3(BFS_THREADS), 0, 0, begin, V, E, nb, split.p);
-        hipLaunchKernelGGL(row_count_flat_kernel, dim3((unsigned) nb), dim3(BFS_THREADS), 0, 0, begin, idx, V, E, (const int64_t*) split.p,
-                           (const uint32_t*) row_bm, (const uint32_t*) probe_bm, invert, cnt, total ? shard.p : nullptr);
-        if (total) hipLaunchKernelGGL(sum_shards_kernel, dim3(1), dim3(64), 0, 0, (const unsigned long long*) shard.p, total);
-        GMX_HIP(hipDeviceSynchronize());   // (split and shard are released here)
-    }
-    GMX_HIP(hipGetLastError());
-    return GMX_OK;
-}
-
-extern "C" int gmx_avg_teen_cnt(gmx_graph_t* g, const int32_t* age_host, int32_t K, int32_t* teen_cnt_host, float* avg,
-                                gmx_stats_t* stats) {
-    GMX_REQUIRE(g && avg && (teen_cnt_host || g->V == 0) && (age_host || g->V == 0), "NULL argument");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    *avg = 0;
-    const int64_t V = g->V;
-    if (V == 0) return GMX_OK;
-    dbuf<int32_t> age, cnt;
-    dbuf<unsigned long long> acc;
-    GMX_CHECK(age.alloc((size_t) V));
-    GMX_CHECK(cnt.alloc((size_t) V));
-    GMX_CHECK(acc.alloc(2));
-    ev_guard evg[2];   // released on every return path
-    hipEvent_t ev[2];
-    for (int i = 0; i < 2; i++) {
-        GMX_CHECK(evg[i].create());
-        ev[i] = evg[i].e;
-    }
-    GMX_HIP(hipMemcpy(age.p, age_host, sizeof(int32_t) * (size_t) V, hipMemcpyHostToDevice));
-    GMX_HIP(hipEventRecord(ev[0], 0));
-    GMX_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (size_t) V, 0));
-    GMX_HIP(hipMemsetAsync(acc.p, 0, 2 * sizeof(unsigned long long), 0));
-    // n.teen_cnt = Count(t: n.InNbrs)(t.age >= 10 && t.age < 20)
-    if (g->has_reverse) {   // as written: every row walks its in-neighbours, the filter being a bitmap in the L2
-        dbuf<unsigned long long> teen;
-        GMX_CHECK(teen.alloc((size_t) ((V + 63) / 64)));
-        hipLaunchKernelGGL(pred_bitmap_kernel, dim3(grid_for(V, BFS_THREADS, 256 * 16)), dim3(BFS_THREADS), 0, 0, (const int32_t*) age.p, V, 0, 0, teen.p);
-        GMX_CHECK(count_by_bitmap(g->r_begin.p, g->r_node_idx.p, V, g->E, nullptr, teen.p, 0, cnt.p, nullptr));
-        GMX_HIP(hipDeviceSynchronize());   // (teen is released at the end of this block)
-    } else {                // forward CSR only: one increment per out-edge of a teen (integer atomics: same counts)
-        GMX_CHECK(expand_selected<0>(g, age.p, 0, 0, cnt.p, nullptr));
-    }
-    // Avg(n: G.Nodes)(n.age > K){n.teen_cnt}: int32 sum, int64 count (gm_syntax_sugar2.cc:264-296)
-    hipLaunchKernelGGL(filtered_sum_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, (const int32_t*) age.p, (const int32_t*) cnt.p,
-                       (const int32_t*) nullptr, V, 0, K, acc.p);
-    GMX_HIP(hipEventRecord(ev[1], 0));
-    unsigned long long h[2];
-    GMX_HIP(hipMemcpy(h, acc.p, sizeof(h), hipMemcpyDeviceToHost));
-    GMX_HIP(hipMemcpy(teen_cnt_host, cnt.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    const int32_t S = (int32_t) (uint32_t) h[0];          // the emitted sum is an int32 and wraps like one
-    const int64_t n = (int64_t) h[1];
-    const double a = (0 == n) ? ((float) (0.000000)) : (S / ((double) n));
-    *avg = (float) a;
-    if (stats) {
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-        stats->iterations = 1;
-        stats->kernel_ms = ms;
-    }
-    return GMX_OK;
-}
-
-extern "C" int gmx_conduct(gmx_graph_t* g, const int32_t* member_host, int32_t num, float* result, gmx_stats_t* stats) {
-    GMX_REQUIRE(g && result && (member_host || g->V == 0), "NULL argument");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    *result = 0;
-    const int64_t V = g->V;
-    unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
-    ev_guard evg[2];   // released on every return path
-    hipEvent_t ev[2];
-    for (int i = 0; i < 2; i++) {
-        GMX_CHECK(evg[i].create());
-        ev[i] = evg[i].e;
-    }
-    if (V > 0) {
-        dbuf<int32_t> member;
-        dbuf<unsigned long long> acc;   // [0,1] Din + count, [2,3] Dout + count, [4] Cross
-        GMX_CHECK(member.alloc((size_t) V));
-        GMX_CHECK(acc.alloc(6));
-        GMX_HIP(hipMemcpy(member.p, member_host, sizeof(int32_t) * (size_t) V, hipMemcpyHostToDevice));
-        GMX_HIP(hipEventRecord(ev[0], 0));
-        GMX_HIP(hipMemsetAsync(acc.p, 0, 6 * sizeof(unsigned long long), 0));
-        hipLaunchKernelGGL(filtered_sum_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, (const int32_t*) member.p, (const int32_t*) nullptr,
-                           (const int32_t*) g->begin.p, V, 1, num, acc.p);
-        hipLaunchKernelGGL(filtered_sum_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, (const int32_t*) member.p, (const int32_t*) nullptr,
-                           (const int32_t*) g->begin.p, V, 2, num, acc.p + 2);
-        {   // Cross: members count their out-neighbours that are not members (membership as a bitmap in the L2)
-            dbuf<unsigned long long> mem_bm;
-            GMX_CHECK(mem_bm.alloc((size_t) ((V + 63) / 64)));
-            hipLaunchKernelGGL(pred_bitmap_kernel, dim3(grid_for(V, BFS_THREADS, 256 * 16)), dim3(BFS_THREADS), 0, 0, (const int32_t*) member.p, V, 1, num, mem_bm.p);
-            GMX_CHECK(count_by_bitmap(g->begin.p, g->node_idx.p, V, g->E, mem_bm.p, mem_bm.p, 1, nullptr, acc.p + 4));
-            GMX_HIP(hipDeviceSynchronize());
-        }
-        GMX_HIP(hipEventRecord(ev[1], 0));
-        GMX_HIP(hipMemcpy(h, acc.p, sizeof(h), hipMemcpyDeviceToHost));
-    }
-    const int32_t Din = (int32_t) (uint32_t) h[0], Dout = (int32_t) (uint32_t) h[2], Cross = (int32_t) (uint32_t) h[4];
-    const float m = (float) ((Din < Dout) ? Din : Dout);
-    if (m == 0) *result = (Cross == 0) ? ((float) (0.000000)) : FLT_MAX;
-    else *result = Cross / m;
-    if (stats && V > 0) {
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-        stats->iterations = 1;
-        stats->kernel_ms = ms;
-    }
-    return GMX_OK;
-}
 
 // Loads this translation unit's code object (the HIP runtime does that lazily, at the first launch of one of its kernels:
 // tens of milliseconds that would otherwise fall into the first timed call) -- called once from the graph constructors.

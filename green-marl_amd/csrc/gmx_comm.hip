@@ -660,21 +660,10 @@ extern "C" int gmx_communities(gmx_graph_t* g, int32_t max_rounds, gmx_node_t* c
     A.ctr = ctr.p;
     A.shard = shard.p;
     A.V = V;
-    struct pinned {
-        comm_rec* p = nullptr;
-        ~pinned() { if (p) (void) hipHostFree(p); }
-    } h_rec;
-    if (hipHostMalloc((void**) &h_rec.p, sizeof(comm_rec), hipHostMallocDefault) != hipSuccess) {
-        h_rec.p = nullptr;
-        gmx_set_error("communities: pinned host allocation failed");
-        return GMX_ERR_HIP;
-    }
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // start, end, download start / end, round
-    struct ev_free {
-        hipEvent_t* e;
-        ~ev_free() { for (int i = 0; i < 5; i++) if (e[i]) (void) hipEventDestroy(e[i]); }
-    } ev_guard{ev};
-    for (hipEvent_t& e : ev) GMX_HIP(hipEventCreate(&e));
+    gmx_pinned<comm_rec> h_rec;
+    GMX_CHECK(h_rec.alloc());
+    gmx_event ev[5];   // start, end, download start / end, round
+    for (gmx_event& e : ev) GMX_CHECK(e.create());
 
     const int word_grid = comm_grid((nwords + COMM_THREADS / 64 - 1) / (COMM_THREADS / 64), 2048);
     const int compact_grid = comm_grid((nwords + COMM_COMPACT_THREADS / 64 - 1) / (COMM_COMPACT_THREADS / 64), 1024);

@@ -137,9 +137,9 @@ extern "C" int gmx_copy_bandwidth(int64_t bytes, int iters, double* gbs) {
     GMX_CHECK(a.alloc((size_t) n));
     GMX_CHECK(b.alloc((size_t) n));
     GMX_HIP(hipMemset(a.p, 1, (size_t) n * 16));
-    hipEvent_t e0, e1;
-    GMX_HIP(hipEventCreate(&e0));
-    GMX_HIP(hipEventCreate(&e1));
+    gmx_event e0, e1;
+    GMX_CHECK(e0.create());
+    GMX_CHECK(e1.create());
     hipLaunchKernelGGL(copy_f32x4_kernel, dim3(256 * 8), dim3(256), 0, 0, (const gmx_f32x4*) a.p, b.p, n);   // warm-up
     (void) hipEventRecord(e0, 0);
     for (int i = 0; i < iters; i++)
@@ -148,8 +148,6 @@ extern "C" int gmx_copy_bandwidth(int64_t bytes, int iters, double* gbs) {
     hipError_t e = hipEventSynchronize(e1);
     float ms = 0;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void) hipEventDestroy(e0);
-    (void) hipEventDestroy(e1);
     GMX_HIP(e);
     *gbs = 2.0 * (double) n * 16.0 * iters / (ms * 1e-3) / 1e9;   // bytes read + bytes written
     return GMX_OK;
@@ -387,6 +385,8 @@ void gmx_warm_modules() {
     gmx_touch_pagerank();
     gmx_touch_pr_cold();
     gmx_touch_bfs();
+    gmx_touch_sssp();
+    gmx_touch_nbrcount();
     gmx_touch_scc();
     gmx_touch_comm();
 }

@@ -69,6 +69,34 @@ struct dbuf {
     T* take() { T* q = p; p = nullptr; n = 0; return q; }
 };
 
+// A hipEvent / pinned host words that are released on every return path.
+struct gmx_event {
+    hipEvent_t e = nullptr;
+    gmx_event() {}
+    gmx_event(gmx_event&& o) : e(o.e) { o.e = nullptr; }
+    gmx_event(const gmx_event&) = delete;
+    gmx_event& operator=(const gmx_event&) = delete;
+    ~gmx_event() { if (e) (void) hipEventDestroy(e); }
+    int create() { GMX_HIP(hipEventCreate(&e)); return GMX_OK; }
+    operator hipEvent_t() const { return e; }
+};
+template <typename T>
+struct gmx_pinned {
+    T* p = nullptr;
+    gmx_pinned() {}
+    gmx_pinned(const gmx_pinned&) = delete;
+    gmx_pinned& operator=(const gmx_pinned&) = delete;
+    ~gmx_pinned() { if (p) (void) hipHostFree(p); }
+    int alloc(size_t count = 1) {
+        if (hipHostMalloc((void**) &p, count * sizeof(T), hipHostMallocDefault) != hipSuccess) {
+            p = nullptr;
+            gmx_set_error("pinned host allocation (%zu bytes) failed", count * sizeof(T));
+            return GMX_ERR_HIP;
+        }
+        return GMX_OK;
+    }
+};
+
 // ---- workspace: where the big temporaries of graph construction and plan builds live ----
 // Device memory that has just been freed is not free: the driver wipes it before it hands it out again, and a
 // hipMalloc that needs such memory waits for the wipe -- measured here as stalls of 1-2.4 s inside an RMAT-26 plan build
@@ -235,6 +263,8 @@ struct gmx_tick {
 void gmx_touch_pagerank();
 void gmx_touch_pr_cold();
 void gmx_touch_bfs();
+void gmx_touch_sssp();
+void gmx_touch_nbrcount();
 void gmx_touch_scc();
 void gmx_touch_comm();
 void gmx_warm_modules();   // once per process: load every translation unit's code object (see gmx_touch_*)

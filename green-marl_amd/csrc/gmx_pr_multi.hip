@@ -379,11 +379,6 @@ __global__ void prm_compare_list_kernel(const uint32_t* __restrict__ a, const ui
     if (c) atomicAdd(bad, c);
 }
 
-struct prm_event {   // released on every return path
-    hipEvent_t e = nullptr;
-    ~prm_event() { if (e) (void) hipEventDestroy(e); }
-};
-
 static int verify_replicas(gmx_pr_multi* m) {
     void* sp = nullptr;
     int64_t slice = 0, need = 0;
@@ -565,11 +560,10 @@ int gmx_pr_multi_run(gmx_pr_multi* m, double e, double d, int32_t max_iter, void
         GMX_HIP(hipSetDevice(m->dev[r]));
         GMX_CHECK(gmx_pr_reset(m->pr[r], d));
     }
-    prm_event g0, g1;
+    gmx_event ev0, ev1;
     GMX_HIP(hipSetDevice(m->dev[0]));
-    GMX_HIP(hipEventCreate(&g0.e));
-    GMX_HIP(hipEventCreate(&g1.e));
-    hipEvent_t ev0 = g0.e, ev1 = g1.e;
+    GMX_CHECK(ev0.create());
+    GMX_CHECK(ev1.create());
     int st = GMX_OK;
     do {
         if ((st = exchange(m))) break;   // the reset filled every rank's own range of the current replica only

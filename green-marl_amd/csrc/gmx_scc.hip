@@ -564,17 +564,14 @@ namespace {
 struct scc_run {
     scc_arrays a{};
     int64_t V = 0;
-    unsigned int* h_ctr = nullptr;   // pinned
+    gmx_pinned<unsigned int> h_ctr;
     int32_t tag = 0;
     int64_t phase_removed[4] = {0, 0, 0, 0};   // trim, FW-BW, colour, tail
     double phase_ms[5] = {0, 0, 0, 0, 0};      // the same + relabel
-    ~scc_run() {
-        if (h_ctr) (void) hipHostFree(h_ctr);
-    }
     int read(unsigned int* dst, int which) {   // synchronises
-        GMX_HIP(hipMemcpyAsync(h_ctr, &a.ctr[which], sizeof(unsigned int), hipMemcpyDeviceToHost, 0));
+        GMX_HIP(hipMemcpyAsync(h_ctr.p, &a.ctr[which], sizeof(unsigned int), hipMemcpyDeviceToHost, 0));
         GMX_HIP(hipStreamSynchronize(0));
-        *dst = *h_ctr;
+        *dst = *h_ctr.p;
         return GMX_OK;
     }
     int clear_q() {
@@ -637,33 +634,21 @@ extern "C" int gmx_scc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
     scc_run R;
     R.V = V;
     R.a = scc_arrays{g->begin.p, g->node_idx.p, g->r_begin.p, g->r_node_idx.p, lab.p, cin.p, cout.p, col.p, mark.p, ctr.p, edges.p};
-    if (hipHostMalloc((void**) &R.h_ctr, 4 * sizeof(unsigned int), hipHostMallocDefault) != hipSuccess) {
-        R.h_ctr = nullptr;
-        gmx_set_error("scc: pinned host allocation failed");
-        return GMX_ERR_HIP;
-    }
+    GMX_CHECK(R.h_ctr.alloc(4));
     const scc_arrays& A = R.a;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct ev_free {
-        hipEvent_t* e;
-        ~ev_free() { for (int i = 0; i < 4; i++) if (e[i]) (void) hipEventDestroy(e[i]); }
-    } ev_guard{ev};
-    for (hipEvent_t& e : ev) GMX_HIP(hipEventCreate(&e));
+    gmx_event ev[4];
+    for (gmx_event& e : ev) GMX_CHECK(e.create());
     GMX_HIP(hipMemsetAsync(ctr.p, 0, sizeof(unsigned int) * C_NCTR, 0));
     GMX_HIP(hipMemsetAsync(edges.p, 0, sizeof(unsigned long long), 0));
     GMX_HIP(hipEventRecord(ev[0], 0));
     // GMX_SCC_PHASES: an event at every phase boundary; the phases' shares of the timed span are added up at the end
-    std::vector<std::pair<hipEvent_t, int>> phase_ev;
-    struct phase_free {
-        std::vector<std::pair<hipEvent_t, int>>* v;
-        ~phase_free() { for (auto& e : *v) (void) hipEventDestroy(e.first); }
-    } phase_guard{&phase_ev};
+    std::vector<std::pair<gmx_event, int>> phase_ev;
     auto phase_end = [&](int ph) {
         if (!phase_log) return;
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return;
+        gmx_event e;
+        if (e.create() != GMX_OK) return;
         (void) hipEventRecord(e, 0);
-        phase_ev.push_back({e, ph});
+        phase_ev.emplace_back(std::move(e), ph);
     };
 
     int64_t live = V;   // vertices not yet removed

@@ -295,7 +295,7 @@ tc_oriented_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict_
             }
             unsigned long long m = __ballot(act && shorter > alone_max);
             while (m) {
-                const int src = __ffsll((long long) m) - 1;
+                const int src = __builtin_ctzll(m);
                 m &= m - 1;
                 const int32_t sbb = __shfl(bb, src, 64), sbe = __shfl(be, src, 64);
                 const int32_t sdb = sbe - sbb, sta = da - (src + 1);
@@ -540,9 +540,9 @@ static int tc_count_part(gmx_graph_t* g, int part, int nparts, bool common_nbr_f
     dbuf<unsigned long long> ctr;   // [0] total, [1] nbig
     GMX_CHECK(ctr.alloc(2));
     GMX_HIP(hipMemset(ctr.p, 0, 2 * sizeof(unsigned long long)));
-    hipEvent_t ev0, ev1;
-    GMX_HIP(hipEventCreate(&ev0));
-    GMX_HIP(hipEventCreate(&ev1));
+    gmx_event ev0, ev1;
+    GMX_CHECK(ev0.create());
+    GMX_CHECK(ev1.create());
     GMX_HIP(hipEventRecord(ev0, 0));
     int64_t blocks = (nlocal + TC_THREADS - 1) / TC_THREADS;
     if (oriented && tc_use_lds()) {
@@ -579,8 +579,6 @@ static int tc_count_part(gmx_graph_t* g, int part, int nparts, bool common_nbr_f
     GMX_HIP(hipEventSynchronize(ev1));
     float ms = 0;
     (void) hipEventElapsedTime(&ms, ev0, ev1);
-    (void) hipEventDestroy(ev0);
-    (void) hipEventDestroy(ev1);
     unsigned long long h = 0;
     GMX_HIP(hipMemcpy(&h, ctr.p, sizeof(h), hipMemcpyDeviceToHost));
     *count = (int64_t) h;
@@ -788,7 +786,7 @@ aa_rows_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ no
             }
             unsigned long long m = __ballot(lead && shorter > alone_max);
             while (m) {
-                const int src = __ffsll((long long) m) - 1;
+                const int src = __builtin_ctzll(m);
                 m &= m - 1;
                 const int32_t stb = __shfl(tb, src, 64), ste = __shfl(te, src, 64);
                 double part = 0.0;
@@ -851,8 +849,8 @@ extern "C" int gmx_adamic_adar(gmx_graph_t* g, double* aa_host, gmx_stats_t* sta
     size_t tb = 0;
     GMX_HIP(rocprim::exclusive_scan(nullptr, tb, groups.p, grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), 0));
     GMX_CHECK(tmp.alloc(tb));
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; i++) GMX_HIP(hipEventCreate(&ev[i]));
+    gmx_event ev[4];
+    for (gmx_event& e : ev) GMX_CHECK(e.create());
     GMX_HIP(hipEventRecord(ev[0], 0));
     GMX_HIP(hipMemsetAsync(ctr.p, 0, 2 * sizeof(unsigned long long), 0));
     GMX_HIP(hipMemsetAsync(groups.p + V, 0, sizeof(int64_t), 0));
@@ -872,7 +870,6 @@ extern "C" int gmx_adamic_adar(gmx_graph_t* g, double* aa_host, gmx_stats_t* sta
     float kms = 0, dms = 0;
     (void) hipEventElapsedTime(&kms, ev[0], ev[1]);
     (void) hipEventElapsedTime(&dms, ev[2], ev[3]);
-    for (int i = 0; i < 4; i++) (void) hipEventDestroy(ev[i]);
     if (stats) {
         stats->kernel_ms = kms;
         stats->d2h_ms = dms;
