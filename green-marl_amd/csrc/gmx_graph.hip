@@ -389,6 +389,7 @@ void gmx_warm_modules() {
     gmx_touch_nbrcount();
     gmx_touch_scc();
     gmx_touch_comm();
+    gmx_touch_pf();
 }
 
 static int check_sizes(int64_t V, int64_t E) {

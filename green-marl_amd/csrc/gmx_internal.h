@@ -267,6 +267,7 @@ void gmx_touch_sssp();
 void gmx_touch_nbrcount();
 void gmx_touch_scc();
 void gmx_touch_comm();
+void gmx_touch_pf();
 void gmx_warm_modules();   // once per process: load every translation unit's code object (see gmx_touch_*)
 
 static inline int gmx_bits_for(int64_t v) {  // bits needed to represent values in [0, v)

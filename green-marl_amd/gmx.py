@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -109,6 +109,7 @@ def lib():
         L.gmx_sssp_path.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(Stats)]
         L.gmx_scc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_communities.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(Stats)]
+        L.gmx_potential_friends.argtypes = [vp, i32, i32, vp, vp, i64, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_avg_teen_cnt.argtypes = [vp, vp, i32, vp, C.POINTER(C.c_float), C.POINTER(Stats)]
         L.gmx_conduct.argtypes = [vp, vp, i32, C.POINTER(C.c_float), C.POINTER(Stats)]
         L.gmx_graph_reverse_edge_map.argtypes = [vp, vp]
@@ -356,6 +357,33 @@ class Graph:
         rounds, conv, st = C.c_int32(0), C.c_int32(0), Stats()
         _ck(lib().gmx_communities(self._h, int(max_rounds), comm.ctypes.data, C.byref(rounds), C.byref(conv), C.byref(st)))
         return comm[:self.V], int(rounds.value), int(conv.value), st.as_dict()
+
+    def _pf_range(self, v_lo, v_hi):
+        v_lo, v_hi = int(v_lo), int(self.V if v_hi is None else v_hi)
+        if not 0 <= v_lo <= v_hi <= self.V:
+            raise GmxError("vertex range [%d, %d) outside [0, %d]" % (v_lo, v_hi, self.V))
+        return v_lo, v_hi
+
+    def potential_friends(self, v_lo=0, v_hi=None):
+        """potential_friends(G, potFriend) for the vertices v_lo <= v < v_hi (v_hi None: V) -- returns (pf_begin[int64],
+        pf_idx[int32], stats): a CSR whose row i is PF(v_lo + i), the out-neighbours of v's out-neighbours that are neither v
+        nor out-neighbours of v, ascending and distinct.  One sizing call, then the filling call; stats are the latter's."""
+        v_lo, v_hi = self._pf_range(v_lo, v_hi)
+        begin = np.zeros(v_hi - v_lo + 1, np.int64)
+        total, st = C.c_int64(0), Stats()
+        _ck(lib().gmx_potential_friends(self._h, v_lo, v_hi, begin.ctypes.data, None, 0, C.byref(total), C.byref(st)))
+        idx = np.zeros(max(total.value, 1), np.int32)
+        _ck(lib().gmx_potential_friends(self._h, v_lo, v_hi, begin.ctypes.data, idx.ctypes.data, total.value, C.byref(total), C.byref(st)))
+        return begin, idx[:total.value], st.as_dict()
+
+    def potential_friend_counts(self, v_lo=0, v_hi=None):
+        """|PF(v)| for v_lo <= v < v_hi as int64[v_hi - v_lo]: the sizing call only.  The run statistics are left in last_stats."""
+        v_lo, v_hi = self._pf_range(v_lo, v_hi)
+        begin = np.zeros(v_hi - v_lo + 1, np.int64)
+        st = Stats()
+        _ck(lib().gmx_potential_friends(self._h, v_lo, v_hi, begin.ctypes.data, None, 0, None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return np.diff(begin)
 
     def avg_teen_cnt(self, age, K):
         """avg_teen_cnt(G, age, teen_cnt, K) -- returns (avg float32, teen_cnt[int32], stats)."""

@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_communities, gmx_potential_friends and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len is indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -274,6 +274,44 @@ int gmx_scc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, gmx_stats_t*
  * comm, vertices_reached = vertex evaluations over all half-rounds, edges_examined = slots read by them. */
 int gmx_communities(gmx_graph_t* g, int32_t max_rounds, gmx_node_t* comm_host /* [V] */,
                     int32_t* rounds, int32_t* converged, gmx_stats_t* stats);
+
+/* potential_friends(G, potFriend) (apps/src/potential_friends.gm:1-8; driver apps/output_cpp/src/potential_friends_main.cc:18):
+ *     Foreach(v) Foreach(u: v.Nbrs)(u != v) Foreach(w: u.Nbrs)(w != u && w != v) If (!v.HasEdgeTo(w)) v.potFriend.Add(w);
+ * the friends of friends that v has no edge to.  u is itself a slot of row(v), so the filters u != v and w != u never change
+ * what is added, and the result is the set
+ *     PF(v) = ( union of row(u) over the slots u of row(v) )  minus  row(v)  minus  {v}.
+ * A set: repeated slots and self loops change nothing.  The result covers the vertices v_lo <= v < v_hi as a CSR:
+ *   pf_begin_host[v_hi - v_lo + 1]   pf_begin[0] = 0, pf_begin[i + 1] - pf_begin[i] = |PF(v_lo + i)|; always written;
+ *   *total                           pf_begin[v_hi - v_lo]; always written (total may be NULL);
+ *   pf_idx_host[cap]                 pf_idx[pf_begin[i] .. pf_begin[i + 1]) = PF(v_lo + i), ASCENDING and distinct (the order in
+ *                                    which gm_node_set iterates, gm_set.h:289-343, in both of its forms).
+ * Sizing protocol, as for gmx_common_nbrs: pf_idx_host is written only when it is not NULL and *total <= cap; otherwise not
+ * one element of it is touched and the call still returns GMX_OK.  The caller sizes with pf_idx_host = NULL, cap = 0 and calls
+ * again.  The sizing call evaluates the set sizes only; it does not pay for a fill.
+ * GMX_ERR_ARG unless 0 <= v_lo <= v_hi <= V, pf_begin_host != NULL and cap >= 0.  An empty range, V = 0 or E = 0: GMX_OK with an
+ * all-zero pf_begin.  The reference decides HasEdgeTo by binary search and needs semi-sorted rows; this entry does not: rows
+ * are read in any order, with repeats, and there is no GMX_ERR_STATE.  Only the forward CSR is read: a GMX_GRAPH_NO_REVERSE
+ * graph gives identical arrays.  Sets and integers only: the result is bit-identical from run to run.  Counts, prefix sums
+ * and two-hop lengths are 64-bit on host and device.
+ * Device memory is bounded whatever the result size: the filled lists are staged in a device buffer of at most
+ * GMX_PF_BATCH_BYTES (default 256 MiB) and copied to pf_idx_host batch by batch over consecutive vertices; a single set
+ * larger than the budget forms a batch of its own.  Everything else (lengths, counts, row lists, bitmaps) comes from the
+ * workspace.
+ * Knobs, read from the environment at every call; the results do not depend on them.  With
+ * L(v) = sum of outdeg(u) over the slots u of row(v), the two-hop items of v:
+ *   GMX_PF_WAVE_MAX    (128)      the largest L evaluated by one wave with a table in LDS;
+ *   GMX_PF_BLOCK_MAX   (2048)     the largest L evaluated by a workgroup with a table in LDS; longer rows use a V-bit map;
+ *   GMX_PF_LDS_SLOTS   (4096)     slots of the workgroup's table, a power of two in [512, 16384] (a wave's table has an
+ *                                 eighth); a row whose table fills is evaluated with a bit map instead;
+ *   GMX_PF_LDS_BITS    (1048576)  the largest V whose bit map stays in LDS (at most 1048576 = 128 KiB); above it every
+ *                                 workgroup of the grid has a map in global memory;
+ *   GMX_PF_BATCH_BYTES.
+ * stats: iterations = batches downloaded (0 for a sizing call), edges_examined = the sum of L(v) over the range (exact),
+ * vertices_reached = vertices of the range with a non-empty set, kernel_ms = device time, d2h_ms = the downloads. */
+int gmx_potential_friends(gmx_graph_t* g, gmx_node_t v_lo, gmx_node_t v_hi,
+                          int64_t* pf_begin_host /* [v_hi - v_lo + 1] */,
+                          gmx_node_t* pf_idx_host /* [cap] or NULL */, int64_t cap,
+                          int64_t* total, gmx_stats_t* stats);
 
 /* triangle_counting(G) with the emitted multiplicity rule. */
 int gmx_triangle_counting(gmx_graph_t* g, int64_t* count, gmx_stats_t* stats);
