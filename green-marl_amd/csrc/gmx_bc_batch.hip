@@ -1,0 +1,507 @@
+// gmx_bc_batch.hip -- comp_BC / bc_random with the sources as the fast axis (gmx_bc_batch, include/gmx.h).
+//
+// gmx_bc (gmx_bfs.hip) sweeps one seed at a time: per row slot an index load, a bitmap probe and a 4- or 8-byte gather for ONE
+// seed.  Here W seeds (16, 32 or 64) share the sweeps: per vertex a row of W level bytes lvl[v][0..W) (0xFF = unreached) and a
+// row of W float2 sd[v][0..W) (x = sigma, y = delta, as bc_visit_fw / bc_visit_rv keep them).  A lane owns one (row, column)
+// sum, so one index load serves W seeds, a gather of lvl[w][.] or sd[w][.] is a fully used line, and the serial chain of float
+// adds that the contract demands (every Sum in row-slot order) runs in W lanes side by side.
+//
+// Per batch: W traversals (the existing one, through gmx_bfs_reach) staged as bytes and transposed once; then one forward pass
+// per level from the roots (sigma) and one reverse pass per level from the deepest (delta), each a launch of its own -- every
+// value a pass reads was written by an earlier launch, nothing is read and written in one launch -- and BC[v] += delta[v][b]
+// for b ascending, which is the per-seed order of the emission.  A pass's rows come from a per-vertex (min, max) level pair
+// and an exact look at the candidates' level rows; rows shorter than GMX_BCB_LONG_MIN slots are walked by a lane group each,
+// the others by a workgroup each whose waves evaluate the terms into LDS for one wave to add in slot order.
+#include "gmx_internal.h"
+#include "gmx_frontier.h"
+
+#include <limits.h>
+
+#define BCB_UNREACHED 0xFFu
+#define BCB_DEPTH_CAP 254       // deepest level a byte holds beside BCB_UNREACHED
+#define BCB_MAX_PASSES (2 * (BCB_DEPTH_CAP + 1))
+#define BCB_FIND_ITEMS 8        // vertices per thread of the row finder (one list append per workgroup and list)
+#define BCB_SHORT_UNROLL 4      // slots of a short row in flight per lane
+#define BCB_LONG_THREADS 1024   // long rows: wave 0 adds, the other 15 waves evaluate terms
+#define BCB_LONG_PRODUCERS (BCB_LONG_THREADS / 64 - 1)
+#define BCB_LONG_UNROLL 8       // 64-lane term rows in flight per producer wave
+#define BCB_LONG_ROWS (BCB_LONG_PRODUCERS * BCB_LONG_UNROLL)   // 64-lane term rows of one LDS tile (two tiles: 60 KiB)
+
+// ---------------------------------------------------------------- levels: dist[] -> stage[b][v] -> lvl[v][b]
+// one traversal's dist[] as bytes, four vertices per thread; its depth and its reached count (one atomic each per workgroup)
+__global__ void __launch_bounds__(BFS_THREADS)
+bcb_stage_kernel(const int32_t* __restrict__ dist, int64_t V, uint32_t* __restrict__ stage_col, int32_t* __restrict__ depth, unsigned long long* __restrict__ reached) {
+    __shared__ int32_t s_depth;
+    __shared__ unsigned int s_reached;
+    if (threadIdx.x == 0) { s_depth = 0; s_reached = 0; }
+    __syncthreads();
+    int32_t d_max = 0;
+    unsigned int n = 0;
+    const int64_t words = (V + 3) >> 2, stride = (int64_t) gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) {
+        uint32_t out = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int64_t v = 4 * i + k;
+            const int32_t d = v < V ? dist[v] : INT_MAX;
+            uint32_t byte = BCB_UNREACHED;
+            if (d != INT_MAX) {
+                n++;
+                d_max = d > d_max ? d : d_max;
+                if (d <= BCB_DEPTH_CAP) byte = (uint32_t) d;   // (a deeper traversal sends its batch to the per-seed path)
+            }
+            out |= byte << (8 * k);
+        }
+        stage_col[i] = out;
+    }
+    atomicMax(&s_depth, d_max);
+    atomicAdd(&s_reached, n);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicMax(depth, s_depth);
+        atomicAdd(reached, (unsigned long long) s_reached);
+    }
+}
+
+// stage[b][v] -> lvl[v][b] through an LDS tile of 256 vertices; columns from nb on (the last, partial batch) are unreached
+// everywhere; minmax[v] = (deepest << 8 | shallowest) level of v over the columns (0x00FF: none)
+template <int W>
+__global__ void __launch_bounds__(256)
+bcb_transpose_kernel(const uint32_t* __restrict__ stage, int64_t V, int64_t pitch_words, int32_t nb, uint32_t* __restrict__ lvl, uint16_t* __restrict__ minmax) {
+    __shared__ uint32_t tile[W][65];   // [column][word of 4 vertices]
+    const int t = threadIdx.x;
+    const int64_t v0 = (int64_t) blockIdx.x * 256;
+#pragma unroll
+    for (int j = 0; j < W / 4; j++) {
+        const int b = (t >> 6) + 4 * j;
+        const int64_t word = (v0 >> 2) + (t & 63);
+        tile[b][t & 63] = (b < nb && 4 * word < V) ? stage[(int64_t) b * pitch_words + word] : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < W / 4; j++) {
+        const int k = t + 256 * j;             // output word of the tile: vertex r, columns c .. c + 3
+        const int r = (4 * k) / W, c = (4 * k) % W;
+        uint32_t out = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) out |= ((tile[c + i][r >> 2] >> (8 * (r & 3))) & 0xFFu) << (8 * i);
+        if (v0 + r < V) lvl[v0 * (W / 4) + k] = out;
+    }
+    if (v0 + t < V) {
+        uint32_t mn = BCB_UNREACHED, mx = 0;
+        for (int b = 0; b < nb; b++) {
+            const uint32_t x = (tile[b][t >> 2] >> (8 * (t & 3))) & 0xFFu;
+            if (x != BCB_UNREACHED) {
+                mn = x < mn ? x : mn;
+                mx = x > mx ? x : mx;
+            }
+        }
+        minmax[v0 + t] = (uint16_t) (mx << 8 | mn);
+    }
+}
+
+// s.sigma = 1 of every column (with skip_root the root is not visited and keeps it; without, pass 0 overwrites it with an
+// empty sum, which is this fork's bc.gm)
+__global__ void bcb_seed_kernel(float2* __restrict__ sd, const int32_t* __restrict__ seeds, int32_t nb, int W) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < nb) sd[(int64_t) seeds[b] * W + b].x = 1.0f;
+}
+
+// ---------------------------------------------------------------- the rows of a pass
+// the vertices with some column at level l, split by the length of the row the pass walks; counts[0 / 1] = short / long rows
+// listed, *slots += their row slots.  A workgroup stages its finds in LDS and appends once per list.
+template <int W>
+__global__ void __launch_bounds__(BFS_THREADS)
+bcb_find_kernel(const uint16_t* __restrict__ minmax, const uint32_t* __restrict__ lvl, const int32_t* __restrict__ begin, int64_t V, int32_t l, int32_t long_min,
+                int32_t* __restrict__ short_list, int32_t* __restrict__ long_list, unsigned int* __restrict__ counts, unsigned long long* __restrict__ slots) {
+    __shared__ int32_t s_list[2][BFS_THREADS * BCB_FIND_ITEMS];
+    __shared__ unsigned int s_n[2], s_base[2];
+    __shared__ unsigned long long s_slots;
+    const int64_t per_block = (int64_t) BFS_THREADS * BCB_FIND_ITEMS;
+    for (int64_t v0 = (int64_t) blockIdx.x * per_block; v0 < V; v0 += (int64_t) gridDim.x * per_block) {   // (workgroup-uniform)
+        if (threadIdx.x == 0) { s_n[0] = s_n[1] = 0; s_slots = 0; }
+        __syncthreads();
+        unsigned long long my_slots = 0;
+#pragma unroll
+        for (int k = 0; k < BCB_FIND_ITEMS; k++) {
+            const int64_t v = v0 + k * BFS_THREADS + threadIdx.x;
+            if (v >= V) continue;
+            const uint32_t mm = minmax[v];
+            if ((int32_t) (mm & 0xFFu) > l || (int32_t) (mm >> 8) < l) continue;
+            bool hit = false;
+#pragma unroll
+            for (int j = 0; j < W / 4; j++) {
+                const uint32_t x = lvl[v * (W / 4) + j];
+#pragma unroll
+                for (int i = 0; i < 4; i++) hit |= ((x >> (8 * i)) & 0xFFu) == (uint32_t) l;
+            }
+            if (!hit) continue;
+            const int32_t deg = begin[v + 1] - begin[v];
+            const int which = deg >= long_min || long_min <= 1;   // (1: every row, the empty ones too)
+            s_list[which][atomicAdd(&s_n[which], 1u)] = (int32_t) v;
+            my_slots += (unsigned long long) deg;
+        }
+        if (my_slots) atomicAdd(&s_slots, my_slots);
+        __syncthreads();
+        if (threadIdx.x < 2 && s_n[threadIdx.x]) s_base[threadIdx.x] = atomicAdd(&counts[threadIdx.x], s_n[threadIdx.x]);
+        if (threadIdx.x == 2 && s_slots) atomicAdd(slots, s_slots);
+        __syncthreads();
+        for (unsigned int i = threadIdx.x; i < s_n[0]; i += BFS_THREADS) short_list[s_base[0] + i] = s_list[0][i];
+        for (unsigned int i = threadIdx.x; i < s_n[1]; i += BFS_THREADS) long_list[s_base[1] + i] = s_list[1][i];
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------- the sums
+// One term of column `col`: forward, sigma of the up-neighbour; reverse, bc_visit_rv::term's own expression (gmx_bfs.hip;
+// the build keeps -ffp-contract=off, so this is a divide, an add and a multiply, each rounded, as the emission has them)
+template <bool FWD>
+__device__ __forceinline__ float bcb_term(float sv, float2 q) {
+    if (FWD) return q.x;
+    return sv / q.x * (1 + q.y);
+}
+
+// short rows: 64 / W rows per wave, lane = (row of the wave, column); every lane walks its row, BCB_SHORT_UNROLL slots in flight
+// (the index loads of a lane group are one address; lvl[w][.] and sd[w][.] are rows of W bytes and W float2).
+// A column that does not pass is SKIPPED (S stays), by a select on the sum: no assumption about the terms is needed here.
+template <int W, bool FWD>
+__global__ void __launch_bounds__(BFS_THREADS)
+bcb_short_kernel(const int32_t* __restrict__ list, const unsigned int* __restrict__ count, const int32_t* __restrict__ begin, const int32_t* __restrict__ idx,
+                 const uint8_t* __restrict__ lvl, float2* __restrict__ sd, int32_t l, int32_t want) {
+    constexpr int G = 64 / W;
+    const int lane = threadIdx.x & 63, col = lane % W, r = lane / W;
+    const unsigned int n = *count, nwaves = gridDim.x * (BFS_THREADS >> 6);
+    for (unsigned int k = blockIdx.x * (BFS_THREADS >> 6) + (threadIdx.x >> 6); (unsigned long long) k * G < n; k += nwaves) {
+        const unsigned int i = k * G + r;
+        if (i >= n) continue;
+        const int32_t v = list[i];
+        const int32_t rb = begin[v], re = begin[v + 1];
+        const int64_t vo = (int64_t) v * W + col;
+        const bool act = lvl[vo] == l;
+        const float sv = FWD ? 0.0f : sd[vo].x;
+        float S = 0.0f;
+        int32_t e = rb;
+        for (; e + BCB_SHORT_UNROLL <= re; e += BCB_SHORT_UNROLL) {
+            int32_t w[BCB_SHORT_UNROLL];
+            int32_t lw[BCB_SHORT_UNROLL];
+            float2 q[BCB_SHORT_UNROLL];
+#pragma unroll
+            for (int j = 0; j < BCB_SHORT_UNROLL; j++) w[j] = idx[e + j];
+#pragma unroll
+            for (int j = 0; j < BCB_SHORT_UNROLL; j++) lw[j] = lvl[(int64_t) w[j] * W + col];
+#pragma unroll
+            for (int j = 0; j < BCB_SHORT_UNROLL; j++) q[j] = (act && lw[j] == want) ? sd[(int64_t) w[j] * W + col] : make_float2(1.0f, 0.0f);
+#pragma unroll
+            for (int j = 0; j < BCB_SHORT_UNROLL; j++) {
+                const float next = S + bcb_term<FWD>(sv, q[j]);
+                S = (act && lw[j] == want) ? next : S;
+            }
+        }
+        for (; e < re; e++) {
+            const int32_t w = idx[e];
+            if (act && lvl[(int64_t) w * W + col] == want) S = S + bcb_term<FWD>(sv, sd[(int64_t) w * W + col]);
+        }
+        if (act) {
+            if (FWD) sd[vo].x = S;
+            else sd[vo].y = S;
+        }
+    }
+}
+
+// long rows: one workgroup per row.  Waves 1 .. 15 evaluate the terms of consecutive slots into an LDS tile [slot][W]
+// (lane = (slot of the wave's 64 / W, column): a tile row of 64 lanes is 64 consecutive words, no bank conflict), 8 tile rows in
+// flight per wave and the next step's indices already requested; wave 0 adds the previous tile in slot order, lane = column
+// (consecutive words again).  Two tiles, one barrier per step: a step's producers write the tile the adder finished before
+// the previous barrier.  Only the adds of a (row, column) are a serial chain; 64 of them run side by side.
+// A column that does not pass is stored as +0.0f and ADDED.  That is bit-safe only because these sums start at +0.0f and their
+// terms are never negative (path counts; sigma > 0 and delta >= 0 on reached vertices) or are NaN (this fork's form, 0 / 0):
+// S is then +0.0f, positive or NaN, and S + (+0.0f) has S's bits -- the NONNEG argument of bfs_ordered_add_dense (gmx_bfs.hip).
+template <int W, bool FWD>
+__global__ void __launch_bounds__(BCB_LONG_THREADS)
+bcb_long_kernel(const int32_t* __restrict__ list, const unsigned int* __restrict__ count, const int32_t* __restrict__ begin, const int32_t* __restrict__ idx,
+                const uint8_t* __restrict__ lvl, float2* __restrict__ sd, int32_t l, int32_t want) {
+    constexpr int G = 64 / W;
+    constexpr int CHUNK = BCB_LONG_ROWS * G;   // slots of a tile
+    __shared__ float tile[2][BCB_LONG_ROWS * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane % W, r = lane / W;
+    const unsigned int n = *count;
+    for (unsigned int k = blockIdx.x; k < n; k += gridDim.x) {   // (workgroup-uniform)
+        const int32_t v = list[k];
+        const int32_t rb = begin[v], deg = begin[v + 1] - rb;
+        const int64_t vo = (int64_t) v * W + col;
+        const bool act = lvl[vo] == l;
+        const float sv = FWD ? 0.0f : sd[vo].x;
+        const int32_t steps = (deg + CHUNK - 1) / CHUNK;
+        float S = 0.0f;
+        int32_t w[BCB_LONG_UNROLL], wn[BCB_LONG_UNROLL];
+        const int32_t first = (wave - 1) * BCB_LONG_UNROLL * G + r;   // the lane's first slot of a tile
+        if (wave > 0) {
+#pragma unroll
+            for (int j = 0; j < BCB_LONG_UNROLL; j++) {
+                const int32_t s = first + j * G;
+                w[j] = deg > 0 ? idx[rb + (s < deg ? s : deg - 1)] : 0;   // (an empty row, GMX_BCB_LONG_MIN=1: no slot to read)
+            }
+        }
+        for (int32_t c = 0; c <= steps; c++) {
+            if (wave > 0 && c < steps) {
+                const int32_t s0 = c * CHUNK + first;
+                int32_t lw[BCB_LONG_UNROLL];
+                float2 q[BCB_LONG_UNROLL];
+                bool pass[BCB_LONG_UNROLL];
+#pragma unroll
+                for (int j = 0; j < BCB_LONG_UNROLL; j++) {   // (the next step's slots, clamped into the row)
+                    const int32_t s = s0 + CHUNK + j * G;
+                    wn[j] = idx[rb + (s < deg ? s : deg - 1)];
+                }
+#pragma unroll
+                for (int j = 0; j < BCB_LONG_UNROLL; j++) lw[j] = lvl[(int64_t) w[j] * W + col];
+#pragma unroll
+                for (int j = 0; j < BCB_LONG_UNROLL; j++) {
+                    pass[j] = act && s0 + j * G < deg && lw[j] == want;
+                    q[j] = pass[j] ? sd[(int64_t) w[j] * W + col] : make_float2(1.0f, 0.0f);
+                }
+#pragma unroll
+                for (int j = 0; j < BCB_LONG_UNROLL; j++) {
+                    tile[c & 1][((wave - 1) * BCB_LONG_UNROLL + j) * 64 + lane] = pass[j] ? bcb_term<FWD>(sv, q[j]) : 0.0f;
+                    w[j] = wn[j];
+                }
+            }
+            if (wave == 0 && c > 0 && lane < W) {
+                const float* t = tile[(c - 1) & 1];
+                const int32_t left = deg - (c - 1) * CHUNK, ns = left < CHUNK ? left : CHUNK;
+                int32_t s = 0;
+                for (; s + 8 <= ns; s += 8) {
+                    float x[8];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) x[j] = t[(s + j) * W + lane];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) S = S + x[j];
+                }
+                for (; s < ns; s++) S = S + t[s * W + lane];
+            }
+            __syncthreads();
+        }
+        if (wave == 0 && lane < W && act) {
+            if (FWD) sd[vo].x = S;
+            else sd[vo].y = S;
+        }
+    }
+}
+
+// v.BC += v.delta of every seed of the batch that reaches v, in seed order (columns ascending); with skip_root not for the
+// seed itself (the one vertex at level 0 of its column)
+template <int W>
+__global__ void __launch_bounds__(BFS_THREADS)
+bcb_accumulate_kernel(const uint32_t* __restrict__ lvl, const float2* __restrict__ sd, int64_t V, int32_t skip_root, float* __restrict__ bc) {
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; v < V; v += stride) {
+        float x = bc[v];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < W / 4; j++) {
+            const uint32_t four = lvl[v * (W / 4) + j];
+            if (four == 0xFFFFFFFFu) continue;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint32_t lv = (four >> (8 * i)) & 0xFFu;
+                if (lv == BCB_UNREACHED || (skip_root && lv == 0)) continue;
+                x = x + sd[v * W + 4 * j + i].y;
+                any = true;
+            }
+        }
+        if (any) bc[v] = x;
+    }
+}
+
+// ---------------------------------------------------------------- host side
+static int64_t bcb_env(const char* name, int64_t dflt, int64_t lo, int64_t hi) {
+    const char* e = getenv(name);
+    if (!e || !*e) return dflt;
+    const long long v = atoll(e);
+    return v < lo ? lo : (v > hi ? hi : (int64_t) v);
+}
+
+// device bytes of a batch of width W on V vertices: sd 8, lvl 1 and the staged levels 1 per (vertex, column); two row lists,
+// minmax and a little padding per vertex (the rule include/gmx.h states for GMX_BCB_MEM_MB)
+static size_t bcb_bytes(int64_t V, int W) { return (size_t) V * (10 * (size_t) W + 10) + 4096 * (size_t) W; }
+
+struct bcb_totals { long long rows_short = 0, rows_long = 0, slots = 0; };
+
+static void bcb_trace(bool on, int64_t batch, int32_t nb, int W, int32_t depth, bool batched, const bcb_totals& t) {
+    if (on) fprintf(stderr, "gmx bc_batch batch %lld: seeds %d width %d depth %d path %s rows %lld short + %lld long, slots %lld\n", (long long) batch, nb, W,
+                    depth, batched ? "batched" : "per-seed", t.rows_short, t.rows_long, t.slots);
+}
+
+struct bcb_knobs {
+    int32_t max_depth, long_min;
+    bool trace;
+};
+
+// the batches of width W; bc (device) is zeroed and then accumulates in seed order.  `started` is recorded once the work
+// buffers exist (no allocation after it)
+template <int W>
+static int bcb_run(gmx_graph* g, const gmx_node_t* seeds, const int32_t* seeds_dev, int32_t nseeds, int skip_root, const bcb_knobs& kn, float* bc,
+                   hipEvent_t started, int64_t* reached_out, int64_t* slots_out) {
+    const int64_t V = g->V;
+    const int64_t pitch_words = ((V + 255) / 256) * 64;   // a staged column, in words of four vertices
+    dbuf<float2> sd;
+    dbuf<uint32_t> lvl, stage;
+    dbuf<uint16_t> minmax;
+    dbuf<int32_t> short_list, long_list, depth;
+    dbuf<unsigned int> counts;             // [pass][2] rows listed
+    dbuf<unsigned long long> tally;        // [0] slots walked, [1 + b] vertices column b reaches
+    GMX_CHECK(sd.alloc((size_t) V * W));
+    GMX_CHECK(lvl.alloc((size_t) V * (W / 4)));
+    GMX_CHECK(stage.alloc((size_t) pitch_words * W));
+    GMX_CHECK(minmax.alloc((size_t) V));
+    GMX_CHECK(short_list.alloc((size_t) V));
+    GMX_CHECK(long_list.alloc((size_t) V));
+    GMX_CHECK(depth.alloc(W));
+    GMX_CHECK(counts.alloc(2 * BCB_MAX_PASSES));
+    GMX_CHECK(tally.alloc(1 + W));
+    std::vector<unsigned int> h_counts(2 * BCB_MAX_PASSES);
+    GMX_HIP(hipEventRecord(started, 0));
+    GMX_HIP(hipMemsetAsync(bc, 0, sizeof(float) * (size_t) V, 0));   // G.BC = 0
+    const uint8_t* lvl8 = (const uint8_t*) lvl.p;
+    const int vblocks = (int) ((V + 255) / 256);
+    const int find_grid = grid_for(V, BFS_THREADS * BCB_FIND_ITEMS, 256 * 8);
+    const int short_grid = grid_for((V + 64 / W - 1) / (64 / W), BFS_THREADS / 64, 256 * 8);
+    const int long_grid = grid_for(V, 1, 256 * 2);
+    int64_t reached = 0, slots = 0;
+    for (int64_t off = 0, batch = 0; off < nseeds; off += W, batch++) {
+        const int32_t nb = (int32_t) (nseeds - off < W ? nseeds - off : W);
+        GMX_HIP(hipMemsetAsync(depth.p, 0, sizeof(int32_t) * W, 0));
+        GMX_HIP(hipMemsetAsync(tally.p, 0, sizeof(unsigned long long) * (1 + W), 0));
+        // the traversals, one seed at a time; a seed deeper than the cap ends them: the batch then runs per seed
+        int32_t deepest = 0;
+        int64_t batch_reached = 0;
+        bool batched = true;
+        for (int32_t b = 0; b < nb && batched; b++) {
+            const int32_t* dist = nullptr;
+            int64_t edges = 0;
+            GMX_CHECK(gmx_bfs_reach(g, seeds[off + b], &dist, &edges));
+            hipLaunchKernelGGL(bcb_stage_kernel, dim3(grid_for((V + 3) / 4)), dim3(BFS_THREADS), 0, 0, dist, V, stage.p + (int64_t) b * pitch_words, depth.p + b, tally.p + 1 + b);
+            int32_t d = 0;
+            unsigned long long r = 0;
+            GMX_HIP(hipMemcpy(&d, depth.p + b, sizeof(d), hipMemcpyDeviceToHost));
+            GMX_HIP(hipMemcpy(&r, tally.p + 1 + b, sizeof(r), hipMemcpyDeviceToHost));
+            deepest = d > deepest ? d : deepest;
+            batch_reached += (int64_t) r;
+            batched = d <= kn.max_depth;
+        }
+        bcb_totals tot;
+        if (!batched) {
+            GMX_CHECK(gmx_bc_seeds(g, seeds + off, nb, skip_root, bc, false, nullptr, &batch_reached));
+            reached += batch_reached;
+            bcb_trace(kn.trace, batch, nb, W, deepest, false, tot);
+            continue;
+        }
+        reached += batch_reached;
+        hipLaunchKernelGGL((bcb_transpose_kernel<W>), dim3(vblocks), dim3(256), 0, 0, (const uint32_t*) stage.p, V, pitch_words, nb, lvl.p, minmax.p);
+        hipLaunchKernelGGL(bcb_seed_kernel, dim3(1), dim3(64), 0, 0, sd.p, seeds_dev + off, nb, W);
+        const int32_t l0 = skip_root ? 1 : 0;   // with skip_root the roots (level 0 of their column) are not visited
+        const int32_t npass = deepest >= l0 ? 2 * (deepest - l0 + 1) : 0;
+        GMX_HIP(hipMemsetAsync(counts.p, 0, sizeof(unsigned int) * 2 * (size_t) (npass > 0 ? npass : 1), 0));
+        int32_t pass = 0;
+        for (int32_t l = l0; l <= deepest; l++, pass++) {   // sigma: the reverse rows, sources one level up
+            unsigned int* cnt = counts.p + 2 * pass;
+            hipLaunchKernelGGL((bcb_find_kernel<W>), dim3(find_grid), dim3(BFS_THREADS), 0, 0, (const uint16_t*) minmax.p, (const uint32_t*) lvl.p, (const int32_t*) g->r_begin.p, V, l,
+                               kn.long_min, short_list.p, long_list.p, cnt, tally.p);
+            hipLaunchKernelGGL((bcb_short_kernel<W, true>), dim3(short_grid), dim3(BFS_THREADS), 0, 0, (const int32_t*) short_list.p, (const unsigned int*) cnt,
+                               (const int32_t*) g->r_begin.p, (const int32_t*) g->r_node_idx.p, lvl8, sd.p, l, l - 1);
+            hipLaunchKernelGGL((bcb_long_kernel<W, true>), dim3(long_grid), dim3(BCB_LONG_THREADS), 0, 0, (const int32_t*) long_list.p, (const unsigned int*) (cnt + 1),
+                               (const int32_t*) g->r_begin.p, (const int32_t*) g->r_node_idx.p, lvl8, sd.p, l, l - 1);
+        }
+        for (int32_t l = deepest; l >= l0; l--, pass++) {   // delta: the forward rows, targets one level down
+            unsigned int* cnt = counts.p + 2 * pass;
+            const int32_t want = l < deepest ? l + 1 : 256;   // (nothing lies below the deepest level; 255 would match BCB_UNREACHED)
+            hipLaunchKernelGGL((bcb_find_kernel<W>), dim3(find_grid), dim3(BFS_THREADS), 0, 0, (const uint16_t*) minmax.p, (const uint32_t*) lvl.p, (const int32_t*) g->begin.p, V, l,
+                               kn.long_min, short_list.p, long_list.p, cnt, tally.p);
+            hipLaunchKernelGGL((bcb_short_kernel<W, false>), dim3(short_grid), dim3(BFS_THREADS), 0, 0, (const int32_t*) short_list.p, (const unsigned int*) cnt,
+                               (const int32_t*) g->begin.p, (const int32_t*) g->node_idx.p, lvl8, sd.p, l, want);
+            hipLaunchKernelGGL((bcb_long_kernel<W, false>), dim3(long_grid), dim3(BCB_LONG_THREADS), 0, 0, (const int32_t*) long_list.p, (const unsigned int*) (cnt + 1),
+                               (const int32_t*) g->begin.p, (const int32_t*) g->node_idx.p, lvl8, sd.p, l, want);
+        }
+        hipLaunchKernelGGL((bcb_accumulate_kernel<W>), dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, (const uint32_t*) lvl.p, (const float2*) sd.p, V, (int32_t) (skip_root != 0), bc);
+        GMX_HIP(hipGetLastError());
+        unsigned long long batch_slots = 0;
+        GMX_HIP(hipMemcpy(&batch_slots, tally.p, sizeof(batch_slots), hipMemcpyDeviceToHost));
+        slots += (int64_t) batch_slots;
+        if (kn.trace) {
+            if (npass > 0) GMX_HIP(hipMemcpy(h_counts.data(), counts.p, sizeof(unsigned int) * 2 * (size_t) npass, hipMemcpyDeviceToHost));
+            for (int32_t p = 0; p < npass; p++) {
+                tot.rows_short += h_counts[2 * (size_t) p];
+                tot.rows_long += h_counts[2 * (size_t) p + 1];
+            }
+            tot.slots = (long long) batch_slots;
+            bcb_trace(true, batch, nb, W, deepest, true, tot);
+        }
+    }
+    *reached_out = reached;
+    *slots_out = slots;
+    return GMX_OK;
+}
+
+#define BCB_DEFAULT_WIDTH 64   // width = 0 without GMX_BCB_WIDTH: the best median at RMAT-24 (the measured table)
+
+extern "C" int gmx_bc_batch(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, int32_t width, float* bc_host, gmx_stats_t* stats) {
+    GMX_REQUIRE(g && bc_host && (seeds || nseeds == 0) && nseeds >= 0, "bad argument");
+    GMX_REQUIRE(width == 0 || width == 1 || width == 16 || width == 32 || width == 64, "width %d: 0, 1, 16, 32 or 64", width);
+    GMX_REQUIRE(g->has_reverse, "comp_BC needs the reverse CSR (UpNbrs)");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const int64_t V = g->V;
+    if (V == 0) return GMX_OK;
+    for (int32_t i = 0; i < nseeds; i++) GMX_REQUIRE(seeds[i] >= 0 && seeds[i] < V, "seed %d out of range", seeds[i]);
+    bcb_knobs kn;
+    kn.max_depth = (int32_t) bcb_env("GMX_BCB_MAX_DEPTH", BCB_DEPTH_CAP, 0, BCB_DEPTH_CAP);   // (the environment lowers it, never raises it)
+    kn.long_min = (int32_t) bcb_env("GMX_BCB_LONG_MIN", 256, 1, INT_MAX);
+    kn.trace = bcb_env("GMX_BCB_TRACE", 0, 0, 1) != 0;
+    int W = width;
+    if (W == 0) {
+        W = (int) bcb_env("GMX_BCB_WIDTH", BCB_DEFAULT_WIDTH, 0, 1 << 20);
+        GMX_REQUIRE(W == 1 || W == 16 || W == 32 || W == 64, "GMX_BCB_WIDTH=%d: 1, 16, 32 or 64", W);
+        while (W > 16 && W / 2 >= nseeds) W /= 2;   // (no wider than the seeds need)
+    }
+    if (W > 1) {   // a batch has to fit: halve the width down to 16, then the per-seed path
+        size_t free_b = 0, total_b = 0;
+        GMX_HIP(hipMemGetInfo(&free_b, &total_b));
+        const int64_t cap_mb = bcb_env("GMX_BCB_MEM_MB", -1, 0, INT64_MAX >> 20);
+        const size_t room = cap_mb >= 0 && (size_t) cap_mb << 20 < free_b ? (size_t) cap_mb << 20 : free_b;
+        while (W >= 16 && bcb_bytes(V, W) > room) W /= 2;
+        if (W < 16) W = 1;
+    }
+    if (W == 1) {   // the existing per-seed path, whole
+        GMX_CHECK(gmx_bc(g, seeds, nseeds, skip_root, bc_host, stats));
+        bcb_trace(kn.trace, 0, nseeds, 1, 0, false, bcb_totals());
+        return GMX_OK;
+    }
+    dbuf<float> bc;
+    dbuf<int32_t> seeds_dev;
+    GMX_CHECK(bc.alloc((size_t) V));
+    GMX_CHECK(seeds_dev.alloc((size_t) nseeds));
+    if (nseeds) GMX_HIP(hipMemcpy(seeds_dev.p, seeds, sizeof(int32_t) * (size_t) nseeds, hipMemcpyHostToDevice));
+    gmx_event e0, e1;
+    GMX_CHECK(e0.create());
+    GMX_CHECK(e1.create());
+    int64_t reached = 0, slots = 0;
+    if (W == 16) GMX_CHECK(bcb_run<16>(g, seeds, seeds_dev.p, nseeds, skip_root, kn, bc.p, e0, &reached, &slots));
+    else if (W == 32) GMX_CHECK(bcb_run<32>(g, seeds, seeds_dev.p, nseeds, skip_root, kn, bc.p, e0, &reached, &slots));
+    else GMX_CHECK(bcb_run<64>(g, seeds, seeds_dev.p, nseeds, skip_root, kn, bc.p, e0, &reached, &slots));
+    GMX_HIP(hipEventRecord(e1, 0));
+    GMX_HIP(hipEventSynchronize(e1));
+    GMX_HIP(hipMemcpy(bc_host, bc.p, sizeof(float) * (size_t) V, hipMemcpyDeviceToHost));
+    if (stats) {
+        float ms = 0;
+        (void) hipEventElapsedTime(&ms, e0, e1);
+        stats->iterations = nseeds;
+        stats->kernel_ms = ms;
+        stats->vertices_reached = reached;
+        stats->edges_examined = slots;
+    }
+    return GMX_OK;
+}
+
+void gmx_touch_bc_batch() {
+    hipFuncAttributes attr;
+    (void) hipFuncGetAttributes(&attr, (const void*) bcb_stage_kernel);
+}

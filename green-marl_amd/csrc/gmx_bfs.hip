@@ -1484,30 +1484,23 @@ __global__ void fill_f32_kernel(float* __restrict__ p, int64_t n, float v, int64
     for (; i < n; i += stride) p[i] = i == one_at ? one_v : v;
 }
 
-extern "C" int gmx_bc(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, float* bc_host, gmx_stats_t* stats) {
-    GMX_REQUIRE(g && bc_host && (seeds || nseeds == 0) && nseeds >= 0, "bad argument");
-    GMX_REQUIRE(g->has_reverse, "comp_BC needs the reverse CSR (UpNbrs)");
-    if (stats) memset(stats, 0, sizeof(*stats));
+// comp_BC's seed loop on a device BC[]: BC[v] = BC[v] + delta_s[v] for every seed in order (gmx_bc below from BC = 0;
+// gmx_bc_batch, gmx_bc_batch.hip, for the batches it does not sweep itself).  `started` (optional) is recorded once the
+// work buffers exist, before the first kernel.
+int gmx_bc_seeds(gmx_graph* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, float* bc_dev, bool zero_bc, hipEvent_t started, int64_t* reached_out) {
     const int64_t V = g->V;
-    if (V == 0) return GMX_OK;
-    for (int32_t i = 0; i < nseeds; i++) GMX_REQUIRE(seeds[i] >= 0 && seeds[i] < V, "seed %d out of range", seeds[i]);
     if (!g->bfs_cache) GMX_CHECK(gmx_bfs_create(g, 0, 1, &g->bfs_cache));
     gmx_bfs* b = g->bfs_cache;
     dbuf<float2> sd;
-    dbuf<float> bc;
     dbuf<int32_t> big_list;
     dbuf<unsigned int> big_count;
     GMX_CHECK(big_list.alloc((size_t) V));
     GMX_CHECK(big_count.alloc(1));
     GMX_CHECK(sd.alloc((size_t) V));
     GMX_HIP(hipMemsetAsync(sd.p, 0, sizeof(float2) * (size_t) V, 0));   // (delta of a vertex no visit has written is never read; zero all the same)
-    GMX_CHECK(bc.alloc((size_t) V));
     bfs_order ord;
-    gmx_event e0, e1;
-    GMX_CHECK(e0.create());
-    GMX_CHECK(e1.create());
-    GMX_HIP(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(fill_f32_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, bc.p, V, 0.0f, (int64_t) -1, 0.0f);   // G.BC = 0
+    if (started) GMX_HIP(hipEventRecord(started, 0));
+    if (zero_bc) hipLaunchKernelGGL(fill_f32_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, bc_dev, V, 0.0f, (int64_t) -1, 0.0f);   // G.BC = 0
     int64_t reached = 0;
     for (int32_t si = 0; si < nseeds; si++) {   // For (s: Seeds.Items): sequential, as emitted
         const gmx_node_t s = seeds[si];
@@ -1516,8 +1509,26 @@ extern "C" int gmx_bc(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, i
         GMX_CHECK(bfs_make_order(b, &ord));
         reached += ord.h_off[(size_t) ord.levels];
         const int32_t skip = skip_root ? s : -1;
-        GMX_CHECK(bfs_sweep(g, b, ord, skip, bc_visit_fw{sd.p}, bc_visit_rv{sd.p, bc.p}, big_list.p, big_count.p));
+        GMX_CHECK(bfs_sweep(g, b, ord, skip, bc_visit_fw{sd.p}, bc_visit_rv{sd.p, bc_dev}, big_list.p, big_count.p));
     }
+    *reached_out = reached;
+    return GMX_OK;
+}
+
+extern "C" int gmx_bc(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, float* bc_host, gmx_stats_t* stats) {
+    GMX_REQUIRE(g && bc_host && (seeds || nseeds == 0) && nseeds >= 0, "bad argument");
+    GMX_REQUIRE(g->has_reverse, "comp_BC needs the reverse CSR (UpNbrs)");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const int64_t V = g->V;
+    if (V == 0) return GMX_OK;
+    for (int32_t i = 0; i < nseeds; i++) GMX_REQUIRE(seeds[i] >= 0 && seeds[i] < V, "seed %d out of range", seeds[i]);
+    dbuf<float> bc;
+    GMX_CHECK(bc.alloc((size_t) V));
+    gmx_event e0, e1;
+    GMX_CHECK(e0.create());
+    GMX_CHECK(e1.create());
+    int64_t reached = 0;
+    GMX_CHECK(gmx_bc_seeds(g, seeds, nseeds, skip_root, bc.p, true, e0, &reached));
     GMX_HIP(hipEventRecord(e1, 0));
     GMX_HIP(hipEventSynchronize(e1));
     GMX_HIP(hipMemcpy(bc_host, bc.p, sizeof(float) * (size_t) V, hipMemcpyDeviceToHost));

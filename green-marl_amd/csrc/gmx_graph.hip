@@ -390,6 +390,7 @@ void gmx_warm_modules() {
     gmx_touch_scc();
     gmx_touch_comm();
     gmx_touch_pf();
+    gmx_touch_bc_batch();
 }
 
 static int check_sizes(int64_t V, int64_t E) {

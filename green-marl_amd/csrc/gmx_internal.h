@@ -180,6 +180,9 @@ struct gmx_graph {
 // root's whole traversal on g's single-rank traversal object (created on first use, as gmx_hop_dist does): *dist = its
 // device dist[] (INT_MAX = unreached, valid until the next traversal on g), *edges = edge slots inspected (gmx_bfs.hip)
 int gmx_bfs_reach(gmx_graph* g, int32_t root, const int32_t** dist, int64_t* edges);
+// comp_BC's per-seed loop on a device BC[V] (zero_bc: G.BC = 0 first); *reached = vertices reached, summed over the seeds.
+// The caller has checked g, the reverse CSR and the seeds (gmx_bfs.hip; gmx_bc and gmx_bc_batch's per-seed batches)
+int gmx_bc_seeds(gmx_graph* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, float* bc_dev, bool zero_bc, hipEvent_t started, int64_t* reached);
 
 // ---- graph construction helpers (gmx_graph.hip) ----
 // keys are (row << 32 | col).  Sorts keys in place (double buffer), then writes
@@ -268,6 +271,7 @@ void gmx_touch_nbrcount();
 void gmx_touch_scc();
 void gmx_touch_comm();
 void gmx_touch_pf();
+void gmx_touch_bc_batch();
 void gmx_warm_modules();   // once per process: load every translation unit's code object (see gmx_touch_*)
 
 static inline int gmx_bits_for(int64_t v) {  // bits needed to represent values in [0, v)

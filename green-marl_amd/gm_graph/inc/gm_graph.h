@@ -50,6 +50,7 @@ class gm_graph
     edge_t get_edge_idx_for_src_dest(node_t src, node_t dest);
 
     node_t num_nodes() { return _numNodes; }
+    node_t pick_random_node() { return rand() % num_nodes(); }   // G.PickRandom(): one libc rand() draw (gm_graph.h:389-391)
     edge_t num_edges() { return _numEdges; }
     bool has_reverse_edge() { return _reverse_edge; }
     bool is_frozen() { return _frozen; }

@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -104,6 +104,7 @@ def lib():
         L.gmx_adamic_adar.argtypes = [vp, vp, C.POINTER(Stats)]
         L.gmx_bfs_levels.argtypes = [vp, i32, vp, C.POINTER(i32)]
         L.gmx_bc.argtypes = [vp, vp, i32, C.c_int, vp, C.POINTER(Stats)]
+        L.gmx_bc_batch.argtypes = [vp, vp, i32, C.c_int, i32, vp, C.POINTER(Stats)]
         L.gmx_triangle_counting.argtypes = [vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_sssp.argtypes = [vp, i32, vp, vp, C.POINTER(Stats)]
         L.gmx_sssp_path.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(Stats)]
@@ -318,6 +319,15 @@ class Graph:
         out = np.zeros(self.V, np.float32)
         st = Stats()
         _ck(lib().gmx_bc(self._h, seeds.ctypes.data if len(seeds) else None, len(seeds), int(bool(skip_root)), out.ctypes.data, C.byref(st)))
+        return out, st.as_dict()
+
+    def bc_batch(self, seeds, skip_root=False, width=0):
+        """gmx_bc_batch: comp_BC with the seeds swept `width` at a time (0: the library's choice) -> (BC[float32], stats);
+        the bytes of bc(seeds, skip_root)."""
+        seeds = _i32(seeds)
+        out = np.zeros(self.V, np.float32)
+        st = Stats()
+        _ck(lib().gmx_bc_batch(self._h, seeds.ctypes.data if len(seeds) else None, len(seeds), int(bool(skip_root)), int(width), out.ctypes.data, C.byref(st)))
         return out, st.as_dict()
 
     def sssp(self, length, root=0):

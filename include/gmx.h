@@ -94,7 +94,7 @@ int gmx_workspace_release(void);
  * have sorted rows.  The other uploads keep the caller's arrays verbatim (with GMX_GRAPH_NO_REVERSE: the forward ones),
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
- *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
+ *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
  *     gmx_scc, gmx_communities, gmx_potential_friends and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len is indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
@@ -198,6 +198,32 @@ int gmx_bfs_download(gmx_bfs_t* b, int32_t* dist_host, gmx_stats_t* stats);
  * reached vertex has a BFS child); skip_root = 1 is upstream Green-Marl's `(v != s)` form.  bc_host[V] is written. */
 int gmx_bfs_levels(gmx_graph_t* g, gmx_node_t root, int16_t* level_host, int32_t* nlevels);
 int gmx_bc(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, float* bc_host, gmx_stats_t* stats);
+
+/* gmx_bc_batch = gmx_bc with the seeds swept `width` at a time (bc_random(G, BC, K) of apps/src/bc_random.gm, driver
+ * apps/output_cpp/src/bc_random_main.cc, draws its K seeds and makes one such call).
+ * Result: bc_host[V] is byte-identical to gmx_bc(g, seeds, nseeds, skip_root, ...) for every width and every knob below.
+ * What that means, per seed s (a column of a batch):
+ *   - sigma[v] is the float sum over v's reverse-row slots whose source is one level up, added in slot order from +0.0f;
+ *   - delta[v] is the float sum over v's forward-row slots whose target is one level down of
+ *     sigma[v] / sigma[w] * (1 + delta[w]), in slot order; repeated slots count repeatedly;
+ *   - BC[v] = BC[v] + delta[v] is applied once per seed, in seed order, only for the seeds that reach v, and with skip_root
+ *     not for v == s;
+ *   - skip_root = 0 is this fork's literal form (bc_random.gm has no (v != s) filter either): every sigma is 0 and the
+ *     result is NaN where a reached vertex has a BFS child;
+ *   - duplicate seeds are independent columns.
+ * width: 0 = the library's choice (GMX_BCB_WIDTH if set, else the measured default, no wider than the seeds need);
+ *   1 = gmx_bc's per-seed path itself; 16, 32, 64 = sources per batch; anything else GMX_ERR_ARG.
+ * The other argument checks, a seed out of range among them, are gmx_bc's, and so is the error for a graph without its reverse CSR.
+ * A batch takes V * (10 * width + 10) + 4096 * width bytes of device memory; when that exceeds the free memory, or
+ * GMX_BCB_MEM_MB (MiB) when set, the width is halved down to 16 and below that the call runs per seed.  A batch in which a
+ * seed's traversal is deeper than GMX_BCB_MAX_DEPTH levels (default and maximum 254: levels are kept as bytes) runs per
+ * seed.  GMX_BCB_LONG_MIN (default 256): rows with at least that many slots are summed by a workgroup, shorter ones by a
+ * lane group (1: every row, empty ones included, by a workgroup).  All are read at every call.  GMX_BCB_TRACE=1 prints one line per batch on stderr:
+ *   gmx bc_batch batch <i>: seeds <n> width <w> depth <d> path <batched|per-seed> rows <s> short + <k> long, slots <n>
+ * stats (may be NULL): iterations = nseeds, vertices_reached = gmx_bc's sum, kernel_ms by events, edges_examined = row
+ * slots the batched sweeps walked (0 on the per-seed path). */
+int gmx_bc_batch(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root,
+                 int32_t width, float* bc_host /* [V] */, gmx_stats_t* stats);
 
 /* sssp(G, dist, len, root) (apps/src/sssp.gm; driver apps/output_cpp/src/sssp_main.cc:42): shortest path lengths
  * over out-edges with the caller's edge property len[E] (indexed by forward edge slot), INT_MAX = unreachable.
