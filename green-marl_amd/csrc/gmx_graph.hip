@@ -391,6 +391,7 @@ void gmx_warm_modules() {
     gmx_touch_comm();
     gmx_touch_pf();
     gmx_touch_bc_batch();
+    gmx_touch_tcd();
 }
 
 static int check_sizes(int64_t V, int64_t E) {
@@ -809,6 +810,8 @@ extern "C" int gmx_graph_free(gmx_graph_t* g) {
         }
         delete g->tc_oriented;
         g->tc_oriented = nullptr;
+        if (g->tcd_cache) gmx_tcd_plan_free(g->tcd_cache);
+        g->tcd_cache = nullptr;
         if (g->bfs_cache) gmx_bfs_free(g->bfs_cache);
         g->bfs_cache = nullptr;
         if (gmx_graph* t = g->scc_transpose) {   // the arrays are g's

@@ -19,25 +19,13 @@
 // counted in its own numbering, as emitted.
 // Integer only: exact.
 #include "gmx_internal.h"
+#include "gmx_tc_search.h"
 
 #include <string.h>
 #include <rocprim/rocprim.hpp>
 
 #define TC_THREADS 256
 #define TC_SMALL 48
-
-__device__ __forceinline__ int32_t tc_lower_bound(const int32_t* __restrict__ a, int32_t lo, int32_t hi, int32_t x) {
-    while (lo < hi) {
-        int32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ bool tc_contains(const int32_t* __restrict__ a, int32_t lo, int32_t hi, int32_t x) {
-    int32_t p = tc_lower_bound(a, lo, hi, x);
-    return p < hi && a[p] == x;
-}
 
 // Multi-GPU: the edge slots are dealt to `nparts` parts in blocks of 2^TC_DEAL_SHIFT slots, round-robin
 // (slot work varies by orders of magnitude with the degrees involved; a contiguous split would leave the
@@ -195,14 +183,6 @@ __global__ void tc_hub_bits_kernel(const int32_t* __restrict__ begin, const int3
         const int64_t w = node_idx[p] - base;   // > row
         atomicOr(&dst[w >> 5], 1u << (w & 31));
     }
-}
-
-__device__ __forceinline__ int32_t tco_lds_lower_bound(const int32_t* a, int32_t lo, int32_t hi, int32_t x) {
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // groups of 64 slots per vertex (a vertex with da upper neighbours has da - 1 slots that can close a triangle)

@@ -1,0 +1,463 @@
+// gmx_tcd.hip -- triangle_counting_directed for gfx950.
+//
+// Replaces the body of apps/src/triangle_counting_directed.gm:
+//     Foreach(v) Foreach(u: v.Nbrs) Foreach(w: v.Nbrs)(w > u)
+//         If (w.HasEdgeFrom(u) || w.HasEdgeTo(u)) T++;
+// With adj(u, w) = (u -> w in E or w -> u in E):
+//     T = sum over v of #{ ordered slot pairs (i, j) of row v : node_idx[i] < node_idx[j], adj(node_idx[i], node_idx[j]) }
+// Repeated slots of row v count multiply, the adjacency test is boolean (set membership, whatever the row order), self
+// loops take part literally (gmx.h).  `w > u` only picks every unordered pair of distinct VALUES of a row once, so T does
+// not depend on the vertex numbering, and the count runs on a renumbered copy.
+//
+// Plan (graph preprocessing: built on first use from the forward CSR alone, cached on the graph, outside kernel_ms):
+//   N      the undirected simple neighbourhood: keys (s,d) and (d,s) of every slot with s != d, sorted, repeats dropped;
+//   perm   ascending |N(x)| (stable: ties by id), or the identity with GMX_TCD_NO_ORDER=1;
+//   OUT'   the forward rows renumbered and sorted, repeats and self loops kept (E entries);
+//   UP'    per vertex x the distinct y > x with adj(x, y), sorted (half of N's entries);
+//   groups exclusive scan of the 64-slot groups of the OUT' rows: a row of d >= 2 slots has ceil((d - 1) / 64) of them
+//          (its last slot has nothing above it).
+// Count: a work item is (v, group of 64 slots of OUT'(v)), claimed from a counter.  The row from the group's first slot on
+// is staged in the wave's LDS slice (at most `cap` entries; longer ones are searched in memory).  Lane i owns the slot
+// u = A[i]; its tail is A from the first position with a value > u (the run of equal values is skipped), the other side is
+// UP'(u).  With the degree order UP'(u) is short for a low-degree u and hubs own almost nothing.  A side of at most
+// `alone` entries is walked by the lane itself; the other slots are taken one after the other by the whole wave, which
+// streams UP'(u) in coalesced pieces and binary-searches the tail while |UP'(u)| <= ratio * |tail|, and streams the tail
+// and searches UP'(u) in memory otherwise.
+// Multiplicity: walking UP'(u) (distinct values), every w found adds its RUN LENGTH in the tail; walking the tail, every
+// slot adds one.  Both give the number of tail slots whose value is in UP'(u).
+// Integer only: exact.  64-bit partials per lane, a shuffle reduction, one atomic add per wave.
+#include "gmx_internal.h"
+#include "gmx_tc_search.h"
+
+#include <rocprim/rocprim.hpp>
+
+#define TCD_THREADS 256
+#define TCD_WAVES 4
+#define TCD_CLAIM 8      // work items per dequeue
+#define TCD_PIECES 4     // 256-byte pieces of UP'(u) a wave keeps in flight
+// alone, ratio and cap are gmx_tc.hip's TCO_ALONE, TCO_RATIO and TCO_CAP, swept here with tools/tcd_prof.py --sweep on directed
+// RMAT-16 and RMAT-20 only; NOT MEASURED: RMAT-22/24, permuted and symmetrised graphs, and TCD_PIECES and
+// TCD_CLAIM above, which are taken over unchanged.
+#define TCD_ALONE 4      // a lane walks a side of up to this many entries by itself (0 .. 16 flat within the spread; 48: +5 %)
+#define TCD_RATIO 4      // stream UP'(u) and search the tail while |UP'(u)| <= TCD_RATIO * |tail| (2 .. 64 flat; 1: +5 %)
+#define TCD_CAP 1024     // row entries staged per wave (4 KiB; 4 waves: 16 KiB of LDS per workgroup; 512: +5 %, 256: +10 %)
+#define TCD_CAP_MIN 64
+
+enum { TCD_TOTAL, TCD_NEXT, TCD_STAGED, TCD_MEMORY, TCD_SLOT_ALONE, TCD_SLOT_LIST, TCD_SLOT_TAIL, TCD_SLOT_EMPTY, TCD_NCTR };
+
+struct tcd_plan {
+    int64_t V = 0, E = 0, E_up = 0;
+    bool ordered = true;
+    double build_ms = 0;
+    dbuf<int32_t> out_begin, out_idx, up_begin, up_idx;
+    dbuf<int64_t> grp_off;   // [V + 1]
+};
+
+void gmx_tcd_plan_free(tcd_plan* p) { delete p; }
+
+// ------------------------------------------------------------------ plan kernels
+static int tcd_grid(int64_t n) {
+    const int64_t b = (n + TCD_THREADS - 1) / TCD_THREADS;
+    return (int) (b < 1 ? 1 : b > 256 * 16 ? 256 * 16 : b);
+}
+
+// both orientations of every slot that is no self loop; `none` (row V: sorts last) for the others
+__global__ void tcd_pair_keys_kernel(const uint64_t* __restrict__ fwd, int64_t E, uint64_t none, uint64_t* __restrict__ out) {
+    int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (; e < E; e += stride) {
+        const uint64_t k = fwd[e];
+        const uint64_t s = k >> 32, d = k & 0xffffffffu;
+        out[2 * e] = s == d ? none : k;
+        out[2 * e + 1] = s == d ? none : ((d << 32) | s);
+    }
+}
+
+// begin[r] = first of the n sorted keys whose row is >= r, r <= V; idx[e] = column of key e, e < nidx
+__global__ void tcd_extract_kernel(const uint64_t* __restrict__ keys, int64_t V, int64_t n, int64_t nidx,
+                                   int32_t* __restrict__ begin, int32_t* __restrict__ idx) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (int64_t e = i; e < nidx; e += stride) idx[e] = (int32_t) (uint32_t) (keys[e] & 0xffffffffu);
+    for (int64_t r = i; r <= V; r += stride) {
+        const uint64_t target = (uint64_t) r << 32;
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (keys[mid] < target) lo = mid + 1; else hi = mid;
+        }
+        begin[r] = (int32_t) lo;
+    }
+}
+
+// ascending |N(x)|, as tc_degkey_kernel does it on a CSR
+__global__ void tcd_degkey_kernel(const int32_t* __restrict__ nbegin, int64_t V, uint32_t* __restrict__ key, int32_t* __restrict__ id) {
+    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (; i < V; i += stride) {
+        key[i] = (uint32_t) nbegin[i + 1] - (uint32_t) nbegin[i];   // (N has up to 2 E < 2^32 entries: the offsets may wrap, the difference does not)
+        id[i] = (int32_t) i;
+    }
+}
+
+__global__ void tcd_invert_kernel(const int32_t* __restrict__ order, int64_t V, int32_t* __restrict__ perm) {
+    int64_t j = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (; j < V; j += stride) perm[order[j]] = (int32_t) j;
+}
+
+// the keys of N, renumbered (perm NULL: as they are): (x, y) with x < y stays, its mirror becomes `none`
+__global__ void tcd_up_keys_kernel(const uint64_t* __restrict__ nkeys, int64_t n, const int32_t* __restrict__ perm, uint64_t none,
+                                   uint64_t* __restrict__ out) {
+    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        const uint64_t k = nkeys[i];
+        uint64_t x = k >> 32, y = k & 0xffffffffu;
+        if (perm) {
+            x = (uint32_t) perm[x];
+            y = (uint32_t) perm[y];
+        }
+        out[i] = x < y ? ((x << 32) | y) : none;
+    }
+}
+
+__global__ void tcd_groups_kernel(const int32_t* __restrict__ begin, int64_t V, int64_t* __restrict__ groups) {
+    int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (; v < V; v += stride) {
+        const int32_t d = begin[v + 1] - begin[v];
+        groups[v] = d >= 2 ? (d - 1 + 63) / 64 : 0;
+    }
+}
+
+// ------------------------------------------------------------------ count kernel
+struct tcd_tally {   // what GMX_TCD_LOG reports: counted where the decisions are taken
+    unsigned long long c = 0;          // per lane
+    unsigned int alone = 0, empty = 0; // per lane
+    unsigned int list = 0, tail = 0;   // per wave (the same in every lane)
+};
+
+// number of entries of R[lo, hi) equal to w (R non-decreasing)
+template <bool LDS>
+__device__ __forceinline__ int32_t tcd_run(const int32_t* R, int32_t lo, int32_t hi, int32_t w) {
+    const int32_t f = LDS ? tco_lds_lower_bound(R, lo, hi, w) : tc_lower_bound(R, lo, hi, w);
+    if (f >= hi || R[f] != w) return 0;
+    if (f + 1 >= hi || R[f + 1] != w) return 1;
+    return (LDS ? tco_lds_lower_bound(R, f + 2, hi, w + 1) : tc_lower_bound(R, f + 2, hi, w + 1)) - f;
+}
+
+// One work item: R[0, da) is OUT'(v) from the group's first slot on (the wave's LDS slice or the row in memory), the
+// group's slots are R[0 .. 63], one per lane; slot i pairs with the entries above its value.
+template <bool LDS>
+__device__ __forceinline__ void tcd_item(const int32_t* R, int32_t da, const int32_t* __restrict__ up_begin,
+                                         const int32_t* __restrict__ up_idx, int lane, int alone_max, int ratio, tcd_tally& t) {
+    const bool act = lane + 1 < da;
+    int32_t bb = 0, be = 0, ts = da;
+    if (act) {
+        const int32_t u = R[lane];
+        ts = LDS ? tco_lds_lower_bound(R, lane + 1, da, u + 1) : tc_lower_bound(R, lane + 1, da, u + 1);
+        bb = up_begin[u];
+        be = up_begin[u + 1];
+    }
+    const int32_t db = be - bb, ta = da - ts;
+    const bool tail_side = ta < db;                     // the side to walk: the shorter one
+    const int32_t shorter = db == 0 || ta == 0 ? 0 : (tail_side ? ta : db);
+    if (act && shorter == 0) t.empty++;
+    if (act && shorter > 0 && shorter <= alone_max) {
+        t.alone++;
+        if (tail_side) {
+            for (int32_t p = ts; p < da; p++) t.c += tc_contains(up_idx, bb, be, R[p]) ? 1 : 0;
+        } else {
+            for (int32_t p = bb; p < be; p++) t.c += (unsigned long long) tcd_run<LDS>(R, ts, da, up_idx[p]);
+        }
+    }
+    unsigned long long m = __ballot(act && shorter > alone_max);
+    while (m) {
+        const int src = __builtin_ctzll(m);
+        m &= m - 1;
+        const int32_t sbb = __shfl(bb, src, 64), sbe = __shfl(be, src, 64), sts = __shfl(ts, src, 64);
+        const int32_t sdb = sbe - sbb, sta = da - sts;
+        if ((long long) sdb <= (long long) ratio * sta) {    // stream UP'(u), search the tail
+            t.list++;
+            for (int32_t p = sbb + lane; p < sbe; p += TCD_PIECES * 64) {
+                int32_t w[TCD_PIECES];
+#pragma unroll
+                for (int k = 0; k < TCD_PIECES; k++) w[k] = p + 64 * k < sbe ? up_idx[p + 64 * k] : -1;
+#pragma unroll
+                for (int k = 0; k < TCD_PIECES; k++) {
+                    if (w[k] < 0) continue;
+                    t.c += (unsigned long long) tcd_run<LDS>(R, sts, da, w[k]);
+                }
+            }
+        } else {                                             // stream the tail, search UP'(u) in memory
+            t.tail++;
+            for (int32_t p = sts + lane; p < da; p += 64) t.c += tc_contains(up_idx, sbb, sbe, R[p]) ? 1 : 0;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(TCD_WAVES * 64)
+tcd_count_kernel(const int32_t* __restrict__ out_begin, const int32_t* __restrict__ out_idx, const int32_t* __restrict__ up_begin,
+                 const int32_t* __restrict__ up_idx, const int64_t* __restrict__ grp_off, int64_t V, int part, int nparts,
+                 int cap /* <= TCD_CAP */, int alone_max, int ratio, unsigned long long* __restrict__ ctr /* [TCD_NCTR] */) {
+    __shared__ int32_t s_row[TCD_WAVES][TCD_CAP];
+    const int lane = threadIdx.x & 63;
+    int32_t* A = s_row[threadIdx.x >> 6];
+    const int64_t G = grp_off[V];
+    const int64_t Q = G > part ? (G - part + nparts - 1) / nparts : 0;   // items part, part + nparts, ...
+    tcd_tally t;
+    unsigned int staged = 0, in_memory = 0;
+    for (;;) {
+        unsigned long long b = 0;
+        if (lane == 0) b = atomicAdd(&ctr[TCD_NEXT], (unsigned long long) TCD_CLAIM);
+        b = __shfl(b, 0, 64);
+        if ((int64_t) b >= Q) break;
+        int64_t v = -1;
+        for (int64_t q = (int64_t) b; q < (int64_t) b + TCD_CLAIM && q < Q; q++) {
+            const int64_t item = q * nparts + part;
+            if (v < 0 || grp_off[v + 1] <= item) {   // vertex of the item: last v with grp_off[v] <= item
+                int64_t lo = 0, hi = V;
+                while (hi - lo > 1) {
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (grp_off[mid] <= item) lo = mid; else hi = mid;
+                }
+                v = lo;
+            }
+            const int32_t ab = out_begin[v] + (int32_t) (item - grp_off[v]) * 64, ae = out_begin[v + 1];
+            const int32_t da = ae - ab;                 // OUT'(v) from the group's first slot on (>= 2)
+            if (da <= cap) {
+                for (int32_t k = lane; k < da; k += 64) A[k] = out_idx[ab + k];
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_s_waitcnt(0xc07f);     // the wave's own LDS writes are visible to all its lanes
+                __builtin_amdgcn_wave_barrier();
+                staged++;
+                tcd_item<true>(A, da, up_begin, up_idx, lane, alone_max, ratio, t);
+                __builtin_amdgcn_wave_barrier();        // all lanes are done with A before it is overwritten
+            } else {
+                in_memory++;
+                tcd_item<false>(out_idx + ab, da, up_begin, up_idx, lane, alone_max, ratio, t);
+            }
+        }
+    }
+    unsigned long long c = t.c, na = t.alone, ne = t.empty;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        c += __shfl_down(c, off, 64);
+        na += __shfl_down(na, off, 64);
+        ne += __shfl_down(ne, off, 64);
+    }
+    if (lane == 0) {
+        if (c) atomicAdd(&ctr[TCD_TOTAL], c);
+        if (staged) atomicAdd(&ctr[TCD_STAGED], (unsigned long long) staged);
+        if (in_memory) atomicAdd(&ctr[TCD_MEMORY], (unsigned long long) in_memory);
+        if (na) atomicAdd(&ctr[TCD_SLOT_ALONE], na);
+        if (t.list) atomicAdd(&ctr[TCD_SLOT_LIST], (unsigned long long) t.list);
+        if (t.tail) atomicAdd(&ctr[TCD_SLOT_TAIL], (unsigned long long) t.tail);
+        if (ne) atomicAdd(&ctr[TCD_SLOT_EMPTY], ne);
+    }
+}
+
+// ------------------------------------------------------------------ host
+// sorts n keys (bits [0, end_bit)) between the two buffers; *sorted = the buffer that holds them, *other = the free one
+static int tcd_sort_keys(uint64_t* a, uint64_t* b, int64_t n, unsigned end_bit, hipStream_t s, uint64_t** sorted, uint64_t** other) {
+    *sorted = a;
+    *other = b;
+    if (n < 2) return GMX_OK;
+    rocprim::double_buffer<uint64_t> db(a, b);
+    size_t tb = 0;
+    GMX_HIP(rocprim::radix_sort_keys(nullptr, tb, db, (size_t) n, 0u, end_bit, s));
+    wbuf<char> tmp;
+    GMX_CHECK(tmp.alloc(tb));
+    GMX_HIP(rocprim::radix_sort_keys((void*) tmp.p, tb, db, (size_t) n, 0u, end_bit, s));
+    GMX_HIP(hipStreamSynchronize(s));
+    *sorted = db.current();
+    *other = db.alternate();
+    return GMX_OK;
+}
+
+static int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
+    const int64_t V = g->V, E = g->E;
+    hipStream_t s = 0;
+    gmx_tick tick("tcd plan");
+    const double t0 = gmx_tick::now();
+    tcd_plan* p = new tcd_plan();
+    struct guard {
+        tcd_plan* p;
+        ~guard() { delete p; }
+    } gd{p};
+    p->V = V;
+    p->E = E;
+    p->ordered = ordered;
+    gmx_ws_scope scope;
+    // the transient keys: 2 E of 64 bits, double-buffered
+    wbuf<uint64_t> ka, kb;
+    const size_t key_bytes = 2 * (size_t) (2 * E) * sizeof(uint64_t);
+    if (ka.alloc((size_t) (2 * E)) || kb.alloc((size_t) (2 * E))) {
+        const std::string why = gmx_last_error();
+        gmx_set_error("triangle_counting_directed: the plan's key buffers need %zu bytes (2 x %lld 64-bit keys): %s", key_bytes,
+                      (long long) (2 * E), why.c_str());
+        return GMX_ERR_NOMEM;
+    }
+    const uint64_t none = (uint64_t) V << 32;
+    const unsigned end_bit = 32 + (unsigned) gmx_bits_for(V + 1);
+    // N: both orientations, sorted, repeats dropped
+    GMX_CHECK(gmx_keys_from_csr(g->begin.p, g->node_idx.p, V, E, false, nullptr, kb.p, s));
+    hipLaunchKernelGGL(tcd_pair_keys_kernel, dim3(tcd_grid(E)), dim3(TCD_THREADS), 0, s, (const uint64_t*) kb.p, E, none, ka.p);
+    GMX_HIP(hipGetLastError());
+    uint64_t *cur = nullptr, *oth = nullptr;
+    GMX_CHECK(tcd_sort_keys(ka.p, kb.p, 2 * E, end_bit, s, &cur, &oth));
+    int64_t n = 0;
+    {
+        wbuf<int64_t> count;
+        wbuf<char> tmp;
+        GMX_CHECK(count.alloc(1));
+        size_t ub = 0;
+        GMX_HIP(rocprim::unique(nullptr, ub, (const uint64_t*) cur, oth, count.p, (size_t) (2 * E), rocprim::equal_to<uint64_t>(), s));
+        GMX_CHECK(tmp.alloc(ub));
+        GMX_HIP(rocprim::unique((void*) tmp.p, ub, (const uint64_t*) cur, oth, count.p, (size_t) (2 * E), rocprim::equal_to<uint64_t>(), s));
+        GMX_HIP(hipMemcpy(&n, count.p, sizeof(int64_t), hipMemcpyDeviceToHost));
+        uint64_t last = 0;   // the self loops' key, if present, is the last one
+        if (n > 0) GMX_HIP(hipMemcpy(&last, oth + (n - 1), sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (n > 0 && last == none) n--;
+    }
+    uint64_t* nkeys = oth;   // n keys of N; `cur` is free
+    tick.mark("N");
+    // perm: ascending |N(x)|
+    wbuf<int32_t> perm;
+    if (ordered) {
+        wbuf<int32_t> nbegin, id, order;
+        wbuf<uint32_t> key, key2;
+        wbuf<char> tmp;
+        GMX_CHECK(nbegin.alloc((size_t) V + 1));
+        GMX_CHECK(id.alloc((size_t) V));
+        GMX_CHECK(order.alloc((size_t) V));
+        GMX_CHECK(key.alloc((size_t) V));
+        GMX_CHECK(key2.alloc((size_t) V));
+        GMX_CHECK(perm.alloc((size_t) V));
+        hipLaunchKernelGGL(tcd_extract_kernel, dim3(tcd_grid(V + 1)), dim3(TCD_THREADS), 0, s, (const uint64_t*) nkeys, V, n, (int64_t) 0, nbegin.p,
+                           (int32_t*) nullptr);
+        hipLaunchKernelGGL(tcd_degkey_kernel, dim3(tcd_grid(V)), dim3(TCD_THREADS), 0, s, (const int32_t*) nbegin.p, V, key.p, id.p);
+        GMX_HIP(hipGetLastError());
+        size_t tb = 0;
+        GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, key.p, key2.p, id.p, order.p, (size_t) V, 0u, 32u, s));
+        GMX_CHECK(tmp.alloc(tb));
+        GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, key.p, key2.p, id.p, order.p, (size_t) V, 0u, 32u, s));
+        hipLaunchKernelGGL(tcd_invert_kernel, dim3(tcd_grid(V)), dim3(TCD_THREADS), 0, s, (const int32_t*) order.p, V, perm.p);
+        GMX_HIP(hipGetLastError());
+    }
+    tick.mark("perm");
+    // UP': the half of N's keys that points upwards in the new numbering
+    p->E_up = n / 2;
+    GMX_CHECK(p->up_begin.alloc((size_t) V + 1));
+    GMX_CHECK(p->up_idx.alloc((size_t) p->E_up));
+    if (n > 0) {
+        hipLaunchKernelGGL(tcd_up_keys_kernel, dim3(tcd_grid(n)), dim3(TCD_THREADS), 0, s, (const uint64_t*) nkeys, n, (const int32_t*) perm.p, none, cur);
+        GMX_HIP(hipGetLastError());
+    }
+    uint64_t *up_sorted = nullptr, *up_free = nullptr;
+    GMX_CHECK(tcd_sort_keys(cur, nkeys, n, end_bit, s, &up_sorted, &up_free));
+    hipLaunchKernelGGL(tcd_extract_kernel, dim3(tcd_grid(p->E_up > V ? p->E_up : V + 1)), dim3(TCD_THREADS), 0, s, (const uint64_t*) up_sorted, V, n,
+                       p->E_up, p->up_begin.p, p->up_idx.p);
+    GMX_HIP(hipGetLastError());
+    GMX_HIP(hipStreamSynchronize(s));
+    tick.mark("UP'");
+    // OUT': the forward rows renumbered and sorted
+    GMX_CHECK(p->out_begin.alloc((size_t) V + 1));
+    GMX_CHECK(p->out_idx.alloc((size_t) E));
+    GMX_CHECK(gmx_keys_from_csr(g->begin.p, g->node_idx.p, V, E, false, perm.p, ka.p, s));
+    GMX_CHECK(gmx_csr_from_keys(ka.p, kb.p, V, E, p->out_begin.p, p->out_idx.p, s));
+    tick.mark("OUT'");
+    // the work items
+    {
+        wbuf<int64_t> groups;
+        wbuf<char> tmp;
+        GMX_CHECK(groups.alloc((size_t) V + 1));
+        GMX_CHECK(p->grp_off.alloc((size_t) V + 1));
+        GMX_HIP(hipMemsetAsync(groups.p + V, 0, sizeof(int64_t), s));
+        hipLaunchKernelGGL(tcd_groups_kernel, dim3(tcd_grid(V)), dim3(TCD_THREADS), 0, s, (const int32_t*) p->out_begin.p, V, groups.p);
+        GMX_HIP(hipGetLastError());
+        size_t tb = 0;
+        GMX_HIP(rocprim::exclusive_scan(nullptr, tb, groups.p, p->grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), s));
+        GMX_CHECK(tmp.alloc(tb));
+        GMX_HIP(rocprim::exclusive_scan((void*) tmp.p, tb, groups.p, p->grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), s));
+        GMX_HIP(hipStreamSynchronize(s));
+    }
+    tick.mark("groups");
+    p->build_ms = (gmx_tick::now() - t0) * 1e3;
+    gd.p = nullptr;
+    *out = p;
+    return GMX_OK;
+}
+
+static int tcd_env(const char* name, int dflt, int lo, int hi) {
+    const char* e = getenv(name);
+    if (!e || !*e) return dflt;
+    const long long v = atoll(e);
+    return (int) (v < lo ? lo : (v > hi ? hi : v));
+}
+
+static int tcd_count_part(gmx_graph_t* g, int part, int nparts, int64_t* count, gmx_stats_t* stats) {
+    GMX_REQUIRE(g && count, "NULL argument");
+    GMX_REQUIRE(nparts >= 1 && part >= 0 && part < nparts, "bad part %d / nparts %d", part, nparts);
+    if (stats) memset(stats, 0, sizeof(*stats));
+    *count = 0;
+    if (g->V == 0 || g->E == 0) return GMX_OK;
+    // knobs, read at every call; the count does not depend on them
+    const bool ordered = !getenv("GMX_TCD_NO_ORDER");
+    const int cap = tcd_env("GMX_TCD_CAP", TCD_CAP, TCD_CAP_MIN, TCD_CAP);
+    const int alone = tcd_env("GMX_TCD_ALONE", TCD_ALONE, 0, INT32_MAX);
+    const int ratio = tcd_env("GMX_TCD_RATIO", TCD_RATIO, 0, INT32_MAX);
+    // graph preprocessing (cached on the graph like the reverse CSR; outside the timed region)
+    bool built = false;
+    if (g->tcd_cache && g->tcd_cache->ordered != ordered) {
+        gmx_tcd_plan_free(g->tcd_cache);
+        g->tcd_cache = nullptr;
+    }
+    if (!g->tcd_cache) {
+        GMX_CHECK(tcd_build_plan(g, ordered, &g->tcd_cache));
+        built = true;
+    }
+    const tcd_plan* p = g->tcd_cache;
+    dbuf<unsigned long long> ctr;
+    GMX_CHECK(ctr.alloc(TCD_NCTR));
+    GMX_HIP(hipMemset(ctr.p, 0, TCD_NCTR * sizeof(unsigned long long)));
+    gmx_event ev0, ev1;
+    GMX_CHECK(ev0.create());
+    GMX_CHECK(ev1.create());
+    GMX_HIP(hipEventRecord(ev0, 0));
+    hipLaunchKernelGGL(tcd_count_kernel, dim3(256 * 8), dim3(TCD_WAVES * 64), 0, 0, (const int32_t*) p->out_begin.p, (const int32_t*) p->out_idx.p,
+                       (const int32_t*) p->up_begin.p, (const int32_t*) p->up_idx.p, (const int64_t*) p->grp_off.p, p->V, part, nparts, cap, alone,
+                       ratio, ctr.p);
+    GMX_HIP(hipGetLastError());
+    GMX_HIP(hipEventRecord(ev1, 0));
+    GMX_HIP(hipEventSynchronize(ev1));
+    float ms = 0;
+    (void) hipEventElapsedTime(&ms, ev0, ev1);
+    unsigned long long h[TCD_NCTR];
+    GMX_HIP(hipMemcpy(h, ctr.p, sizeof(h), hipMemcpyDeviceToHost));
+    *count = (int64_t) h[TCD_TOTAL];
+    if (stats) {
+        stats->iterations = 1;
+        stats->kernel_ms = ms;
+    }
+    if (getenv("GMX_TCD_LOG"))   // one line per call (tools/tcd_prof.py and the tests parse it)
+        fprintf(stderr, "gmx triangle_counting_directed: plan V %lld out %lld up %lld order %s built %d build_ms %.3f; part %d/%d cap %d alone %d "
+                        "ratio %d; items %llu staged + %llu memory; slots %llu alone + %llu list + %llu tail + %llu empty\n",
+                (long long) p->V, (long long) p->E, (long long) p->E_up, p->ordered ? "degree" : "identity", built ? 1 : 0, built ? p->build_ms : 0.0,
+                part, nparts, cap, alone, ratio, h[TCD_STAGED], h[TCD_MEMORY], h[TCD_SLOT_ALONE], h[TCD_SLOT_LIST], h[TCD_SLOT_TAIL], h[TCD_SLOT_EMPTY]);
+    return GMX_OK;
+}
+
+extern "C" int gmx_triangle_counting_directed(gmx_graph_t* g, int64_t* count, gmx_stats_t* stats) {
+    return tcd_count_part(g, 0, 1, count, stats);
+}
+
+extern "C" int gmx_triangle_counting_directed_part(gmx_graph_t* g, int part, int nparts, int64_t* count, gmx_stats_t* stats) {
+    return tcd_count_part(g, part, nparts, count, stats);
+}
+
+void gmx_touch_tcd() {
+    hipFuncAttributes attr;
+    (void) hipFuncGetAttributes(&attr, (const void*) tcd_count_kernel);
+}

@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -119,6 +119,8 @@ def lib():
         L.gmx_graph_edge_order_e64.argtypes = [vp, vp, C.POINTER(C.c_int)]
         L.gmx_graph_reverse_edge_map_e64.argtypes = [vp, vp]
         L.gmx_triangle_counting_part.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_triangle_counting_directed.argtypes = [vp, C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_triangle_counting_directed_part.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_bfs_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
         L.gmx_bfs_free.argtypes = [vp]
         L.gmx_bfs_start.argtypes = [vp, i32]
@@ -461,6 +463,14 @@ class Graph:
         t = C.c_int64(0)
         st = Stats()
         _ck(lib().gmx_triangle_counting_part(self._h, part, nparts, C.byref(t), C.byref(st)))
+        return t.value, st.as_dict()
+
+    def triangle_counting_directed(self, part=0, nparts=1):
+        """triangle_counting_directed(G): the slot pairs (u, w), u < w, of every row whose two ends are joined by an edge in
+        either direction -- returns (T, stats); with nparts > 1 the share of one part of the work items.  Any row order."""
+        t = C.c_int64(0)
+        st = Stats()
+        _ck(lib().gmx_triangle_counting_directed_part(self._h, part, nparts, C.byref(t), C.byref(st)))
         return t.value, st.as_dict()
 
 

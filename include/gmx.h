@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_communities, gmx_potential_friends and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len is indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -344,6 +344,37 @@ int gmx_triangle_counting(gmx_graph_t* g, int64_t* count, gmx_stats_t* stats);
 /* Multi-GPU form (replicated CSR, final all-reduce of int64): the count contributed by part
  * `part` of `nparts` of the edge slots (dealt in blocks, round-robin); the parts add up to the full count. */
 int gmx_triangle_counting_part(gmx_graph_t* g, int part, int nparts, int64_t* count, gmx_stats_t* stats);
+
+/* triangle_counting_directed(G) (apps/src/triangle_counting_directed.gm):
+ *     Foreach(v) Foreach(u: v.Nbrs) Foreach(w: v.Nbrs)(w > u)
+ *         If (w.HasEdgeFrom(u) || w.HasEdgeTo(u)) T++;
+ * With adj(u, w) = (u -> w in E or w -> u in E):
+ *     T = sum over v of #{ ordered slot pairs (i, j) of row v : node_idx[i] < node_idx[j], adj(node_idx[i], node_idx[j]) }.
+ *   - Repeated slots of row v count multiply, as in gmx_triangle_counting; the adjacency test is boolean.
+ *   - Self loops take part literally: with v in row(v), every pair (v, w) with w != v of that row counts, because v -> w
+ *     exists.  A pair needs two distinct values, so a self loop alone adds nothing.
+ *   - HasEdgeTo / HasEdgeFrom are set membership: the reference binary-searches a semi-sorted row (gm_graph.cc:60-66) and
+ *     its generated prologue semi-sorts, so on rows in any order the result is defined by membership, not by a failed search.
+ *   - `w > u` only picks every unordered pair of distinct values of a row once: T does not depend on the vertex numbering.
+ *   - On a symmetric graph without self loops and repeated slots T = 3 x gmx_triangle_counting: every triangle is seen
+ *     once from each corner.
+ * g == NULL, count == NULL or a part outside [0, nparts): GMX_ERR_ARG.  V = 0 or E = 0: GMX_OK with *count = 0.  Rows are
+ * read in any order, with repeats, and only the forward CSR is read: a GMX_GRAPH_NO_REVERSE graph works and there is no
+ * GMX_ERR_STATE.  The first call on a graph builds a plan from the forward CSR (two CSRs renumbered by ascending undirected
+ * degree and the work items), cached on the graph and freed with it; its transient buffers are 2 x 2E
+ * 64-bit keys, and when they or the plan cannot be allocated the call returns GMX_ERR_NOMEM and the message says how many
+ * bytes were asked for.  Integers only: the count is exact and the same from run to run.
+ * gmx_triangle_counting_directed_part: the work items (a vertex and 64 slots of its row) are dealt round-robin to nparts
+ * parts; the parts' counts add up to the whole for any nparts.
+ * Knobs, read from the environment at every call; the count does not depend on them:
+ *   GMX_TCD_NO_ORDER=1   the plan keeps the graph's numbering (the cached plan is rebuilt when the knob changes);
+ *   GMX_TCD_CAP          (1024) row entries a wave stages in LDS, clamped to [64, 1024]; longer rows are searched in memory;
+ *   GMX_TCD_ALONE        (4) a lane walks a side of up to this many entries by itself;
+ *   GMX_TCD_RATIO        (4) a wave streams the upper list of u while it is at most this many times the tail of the row;
+ *   GMX_TCD_LOG=1        one line on stderr per call: the plan, the work items staged and in memory, the slots per regime.
+ * stats: iterations = 1, kernel_ms = the count kernel only (the plan is graph preprocessing); everything else zero. */
+int gmx_triangle_counting_directed(gmx_graph_t* g, int64_t* count, gmx_stats_t* stats);
+int gmx_triangle_counting_directed_part(gmx_graph_t* g, int part, int nparts, int64_t* count, gmx_stats_t* stats);
 
 /* The common-neighbour iterator, gm_common_neighbor_iter(G, s, d) (gm_common_neighbor_iter.cc:21-44): the slots of s's
  * row, in order and with their multiplicity, whose value occurs in d's row (Foreach(u: s.CommonNbrs(d)) <=>
