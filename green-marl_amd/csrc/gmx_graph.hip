@@ -392,6 +392,7 @@ void gmx_warm_modules() {
     gmx_touch_pf();
     gmx_touch_bc_batch();
     gmx_touch_tcd();
+    gmx_touch_vcover();
 }
 
 static int check_sizes(int64_t V, int64_t E) {
@@ -812,6 +813,8 @@ extern "C" int gmx_graph_free(gmx_graph_t* g) {
         g->tc_oriented = nullptr;
         if (g->tcd_cache) gmx_tcd_plan_free(g->tcd_cache);
         g->tcd_cache = nullptr;
+        if (g->vc_cache) gmx_vc_plan_free(g->vc_cache);
+        g->vc_cache = nullptr;
         if (g->bfs_cache) gmx_bfs_free(g->bfs_cache);
         g->bfs_cache = nullptr;
         if (gmx_graph* t = g->scc_transpose) {   // the arrays are g's

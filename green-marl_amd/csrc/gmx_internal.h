@@ -136,6 +136,8 @@ struct wbuf {
 struct gmx_bfs;
 struct tcd_plan;
 void gmx_tcd_plan_free(tcd_plan* p);   // gmx_tcd.hip
+struct vc_plan;
+void gmx_vc_plan_free(vc_plan* p);     // gmx_vcover.hip
 
 struct gmx_graph {
     int64_t V = 0, E = 0;
@@ -166,6 +168,9 @@ struct gmx_graph {
     // triangle_counting_directed: the two renumbered CSRs and the work items (gmx_tcd.hip), built on first use; the plan
     // records the order it was built with
     tcd_plan* tcd_cache = nullptr;
+    // v_cover: Deg0, the incident lists sorted by (Deg0 of the other end descending, uploaded slot ascending), their offsets
+    // and the lowest incident slot per vertex (gmx_vcover.hip), built on first use
+    vc_plan* vc_cache = nullptr;
     // hop_dist: the single-rank traversal state (queues, bitmaps, dist[]) of the whole-kernel entry, kept for the
     // next call on the same graph instead of nine allocations per call
     gmx_bfs* bfs_cache = nullptr;
@@ -278,6 +283,7 @@ void gmx_touch_comm();
 void gmx_touch_pf();
 void gmx_touch_bc_batch();
 void gmx_touch_tcd();
+void gmx_touch_vcover();
 void gmx_warm_modules();   // once per process: load every translation unit's code object (see gmx_touch_*)
 
 static inline int gmx_bits_for(int64_t v) {  // bits needed to represent values in [0, v)

@@ -95,8 +95,8 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
- *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len is indexed by the stored slots);
+ *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len and gmx_v_cover's select are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
  *     gm_common_neighbor_iter.h): GMX_ERR_STATE when the forward rows are not sorted.  With sorted forward rows and an
@@ -403,6 +403,33 @@ int gmx_triangle_counting_cn(gmx_graph_t* g, int64_t* count, gmx_stats_t* stats)
  * GMX_ERR_STATE, as for the iterator.  E = 0: GMX_OK, nothing written.  stats: iterations = 1, kernel_ms = device time
  * (weights, work list and the intersections), d2h_ms = download of aa, edges_examined = items over all slots (exact). */
 int gmx_adamic_adar(gmx_graph_t* g, double* aa_host /* [E] */, gmx_stats_t* stats);
+
+/* v_cover(G, select) (apps/src/v_cover.gm; driver apps/output_cpp/src/v_cover_main.cc:24): the greedy vertex cover
+ *     Deg = Degree() + InDegree();  Covered = select = False;  remain = 2 E;
+ *     While (remain > 0) { the edge s -> t with !(Covered[s] && Covered[t]) of maximal Deg[s] + Deg[t] is selected;
+ *                          remain -= that maximum;  Deg[s] = Deg[t] = 0;  Covered[s] = Covered[t] = True; }
+ *     Return Count(Covered);
+ * The reference's parallel arg-max breaks ties by thread timing (its driver prints "may be non-deterministic").  The
+ * device is deterministic and equal to the reference run with ONE thread: among the edges of maximal Deg[s] + Deg[t] the
+ * lowest forward slot wins.  Everything else is literal: duplicate edges are separate slots, and a selected self loop
+ * takes 2 Deg[s] from `remain` but only Deg[s] from the degree sum, so the loop can stop with uncovered vertices left.
+ * `remain` is kept in 64 bits here; the reference's Int overflows from E = 2^30 upward, and this entry takes E < 2^30
+ * (GMX_ERR_ARG otherwise: the incident lists keep 32-bit offsets).
+ * select_host[E] (0 / 1) is indexed, and ties are decided, by the UPLOADED slots like gmx_sssp's len (through e_idx2idx
+ * when the upload sorted the rows): the result is the same for every upload form, and rows are read in any order.
+ * *covered = the number of covered vertices.  Needs the reverse CSR (GMX_ERR_STATE after an upload with
+ * GMX_GRAPH_NO_REVERSE).  g == NULL, covered == NULL, or select_host == NULL with E > 0: GMX_ERR_ARG.  V = 0 or E = 0:
+ * GMX_OK, *covered = 0, select_host untouched.
+ * The arg-max per selected edge is replaced by rounds that pick every locally dominant edge at once, O(E) work in total
+ * (gmx_vcover.hip); the first call builds a plan (per vertex its incident edges sorted by the other
+ * end's degree), cached on the graph and freed with it.  Read at every call, the result does not depend on them:
+ *   GMX_VC_TAIL  a round with at most this many active vertices hands the rest to one workgroup (0: never; huge: all),
+ *   GMX_VC_WAVE  a list with at least this many entries left is advanced by a wave (0: always; huge: always a lane),
+ *   GMX_VC_LOG=1 one stderr line per call: plan built / reused, V, E, list entries, rounds, picks, kept, counters, ms.
+ * stats: iterations = parallel rounds, kernel_ms = device time without the plan build, edges_examined = list entries
+ * skipped + vertex evaluations + list entries walked, vertices_reached = covered, edges_reached = selected edges,
+ * d2h_ms = download of select. */
+int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host /* [E], uploaded slots, 0/1 */, int32_t* covered, gmx_stats_t* stats);
 
 /* ---- device-resident PageRank stepping (bench.py / multi-GPU driver) ----
  * A gmx_pr_t owns the rows [row_lo,row_hi) of the (internally relabelled) graph
