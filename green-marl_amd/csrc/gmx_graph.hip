@@ -393,6 +393,7 @@ void gmx_warm_modules() {
     gmx_touch_bc_batch();
     gmx_touch_tcd();
     gmx_touch_vcover();
+    gmx_touch_match();
 }
 
 static int check_sizes(int64_t V, int64_t E) {

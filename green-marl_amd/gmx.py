@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -103,6 +103,7 @@ def lib():
         L.gmx_triangle_counting_cn.argtypes = [vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_adamic_adar.argtypes = [vp, vp, C.POINTER(Stats)]
         L.gmx_v_cover.argtypes = [vp, vp, C.POINTER(i32), C.POINTER(Stats)]
+        L.gmx_random_bipartite_matching.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_bfs_levels.argtypes = [vp, i32, vp, C.POINTER(i32)]
         L.gmx_bc.argtypes = [vp, vp, i32, C.c_int, vp, C.POINTER(Stats)]
         L.gmx_bc_batch.argtypes = [vp, vp, i32, C.c_int, i32, vp, C.POINTER(Stats)]
@@ -466,6 +467,19 @@ class Graph:
         cov, st = C.c_int32(0), Stats()
         _ck(lib().gmx_v_cover(self._h, sel.ctypes.data if self.E else None, C.byref(cov), C.byref(st)))
         return sel[:self.E].astype(bool), int(cov.value), st.as_dict()
+
+    def random_bipartite_matching(self, is_left):
+        """random_bipartite_matching(G, isLeft, Match): the maximal matching as one thread of the reference runs it (a right
+        takes its largest proposing left, a left its largest replying right) -- returns (match[int32, V] with -1 for the
+        unmatched, count, stats).  Only rows of left vertices are read, forward CSR only, any row order."""
+        left = np.ascontiguousarray(np.asarray(is_left) != 0, np.uint8)
+        if left.shape != (self.V,):
+            raise ValueError("is_left must have one entry per vertex")
+        match = np.full(max(self.V, 1), -1, np.int32)
+        cnt, st = C.c_int32(0), Stats()
+        _ck(lib().gmx_random_bipartite_matching(self._h, left.ctypes.data if self.V else None, match.ctypes.data if self.V else None,
+                                                C.byref(cnt), C.byref(st)))
+        return match[:self.V], int(cnt.value), st.as_dict()
 
     def triangle_counting(self, part=0, nparts=1):
         """triangle_counting(G) -- returns (T, stats); with nparts > 1 the share of one part of the edge slots."""

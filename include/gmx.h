@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len and gmx_v_cover's select are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -430,6 +430,36 @@ int gmx_adamic_adar(gmx_graph_t* g, double* aa_host /* [E] */, gmx_stats_t* stat
  * skipped + vertex evaluations + list entries walked, vertices_reached = covered, edges_reached = selected edges,
  * d2h_ms = download of select. */
 int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host /* [E], uploaded slots, 0/1 */, int32_t* covered, gmx_stats_t* stats);
+
+/* random_bipartite_matching(G, isLeft, Match) (apps/src/random_bipartite_matching.gm; the reference ships no driver): a
+ * maximal matching of a bipartite graph whose edges lead from left to right vertices, by rounds of
+ *     1. proposals: every unmatched left n sets Suitor[t] = n at every unmatched neighbour t (an intended write-write race);
+ *     2. replies:   every unmatched right t with a suitor n sets Suitor[n] = t and clears its own;
+ *     3. commit:    every left n with a reply t: Match[n] = t, Match[t] = n, count++;
+ * until a round makes no proposal.  The race makes a parallel reference run depend on thread timing.  The device is
+ * deterministic and equal to the reference run with ONE thread: Foreach visits vertices in ascending id and a row in slot
+ * order, so the last writer wins -- Suitor[t] is the LARGEST unmatched left n with an edge n -> t, and a left keeps the
+ * LARGEST right that replied to it.  *count = the matched pairs (the program's return value); match_host[v] = the partner
+ * of v, -1 (gm_graph::NIL_NODE) for every vertex left unmatched.  Suitor is internal.
+ * Only rows of vertices with is_left != 0 are read: edges out of right vertices, right self loops included, are ignored as
+ * the literal loop ignores them; duplicate slots are harmless.  An edge from a left to a left vertex breaks the program's
+ * precondition ("every edge is from left node to right node"): GMX_ERR_ARG, gmx_last_error() names one such edge, and
+ * match_host is untouched (found on the device by the first proposal pass, not by a sweep of its own).
+ * Only the forward CSR is read (a GMX_GRAPH_NO_REVERSE graph works), rows in any order, repeats included; the result is
+ * indexed by vertex and so the same for every upload form.  g == NULL, count == NULL, or is_left_host / match_host ==
+ * NULL with V > 0: GMX_ERR_ARG.  V = 0: GMX_OK, *count = 0.  E = 0: GMX_OK, all -1.  Nothing is cached on the graph.
+ * A round is three launches over lists (the rows of the live lefts, the rights that got a proposal, the live lefts);
+ * a left is live while it is unmatched and proposed in the round before (gmx_match.hip).  Read at every
+ * call, the result does not depend on them:
+ *   GMX_RBM_TAIL   once the live rows hold at most this many slots one workgroup runs the rest (0: never; huge: all),
+ *   GMX_RBM_LOG=1  one stderr line per call: V, E, lefts, the threshold, rounds grid + tail, matched, proposals, slots, ms
+ *                  (2: before it a line per grid round: live lefts, slots, proposals, touched rights, host-clock ms).
+ * stats: iterations = rounds that made a proposal, vertices_reached = *count, edges_reached = proposals summed over the
+ * rounds (a proposal is a slot (n, t) of a live left with t unmatched at the round's start: schedule-independent),
+ * edges_examined = slots read, h2d_ms = upload of is_left, d2h_ms = download of match, kernel_ms = device time from the
+ * first to the last launch. */
+int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_left_host /* [V], 0/1 */,
+                                  gmx_node_t* match_host /* [V], partner or -1 */, int32_t* count, gmx_stats_t* stats);
 
 /* ---- device-resident PageRank stepping (bench.py / multi-GPU driver) ----
  * A gmx_pr_t owns the rows [row_lo,row_hi) of the (internally relabelled) graph
