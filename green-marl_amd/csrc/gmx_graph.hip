@@ -394,6 +394,7 @@ void gmx_warm_modules() {
     gmx_touch_tcd();
     gmx_touch_vcover();
     gmx_touch_match();
+    gmx_touch_spf();
 }
 
 static int check_sizes(int64_t V, int64_t E) {
@@ -816,6 +817,8 @@ extern "C" int gmx_graph_free(gmx_graph_t* g) {
         g->tcd_cache = nullptr;
         if (g->vc_cache) gmx_vc_plan_free(g->vc_cache);
         g->vc_cache = nullptr;
+        if (g->spf_cache) gmx_spf_scratch_free(g->spf_cache);
+        g->spf_cache = nullptr;
         if (g->bfs_cache) gmx_bfs_free(g->bfs_cache);
         g->bfs_cache = nullptr;
         if (gmx_graph* t = g->scc_transpose) {   // the arrays are g's

@@ -138,6 +138,8 @@ struct tcd_plan;
 void gmx_tcd_plan_free(tcd_plan* p);   // gmx_tcd.hip
 struct vc_plan;
 void gmx_vc_plan_free(vc_plan* p);     // gmx_vcover.hip
+struct spf_scratch;
+void gmx_spf_scratch_free(spf_scratch* s);   // gmx_sssp_f64.hip
 
 struct gmx_graph {
     int64_t V = 0, E = 0;
@@ -171,6 +173,8 @@ struct gmx_graph {
     // v_cover: Deg0, the incident lists sorted by (Deg0 of the other end descending, uploaded slot ascending), their offsets
     // and the lowest incident slot per vertex (gmx_vcover.hip), built on first use
     vc_plan* vc_cache = nullptr;
+    // sssp_path_f64: the per-vertex words, lists and the cost copies of a call (gmx_sssp_f64.hip), allocated on first use
+    spf_scratch* spf_cache = nullptr;
     // hop_dist: the single-rank traversal state (queues, bitmaps, dist[]) of the whole-kernel entry, kept for the
     // next call on the same graph instead of nine allocations per call
     gmx_bfs* bfs_cache = nullptr;
@@ -285,6 +289,7 @@ void gmx_touch_bc_batch();
 void gmx_touch_tcd();
 void gmx_touch_vcover();
 void gmx_touch_match();
+void gmx_touch_spf();
 void gmx_warm_modules();   // once per process: load every translation unit's code object (see gmx_touch_*)
 
 static inline int gmx_bits_for(int64_t v) {  // bits needed to represent values in [0, v)

@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -110,6 +110,7 @@ def lib():
         L.gmx_triangle_counting.argtypes = [vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_sssp.argtypes = [vp, i32, vp, vp, C.POINTER(Stats)]
         L.gmx_sssp_path.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(Stats)]
+        L.gmx_sssp_path_f64.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.POINTER(Stats)]
         L.gmx_scc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_communities.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_potential_friends.argtypes = [vp, i32, i32, vp, vp, i64, C.POINTER(i64), C.POINTER(Stats)]
@@ -354,6 +355,21 @@ class Graph:
         st = Stats()
         _ck(lib().gmx_sssp_path(self._h, int(root), length.ctypes.data if self.E else None, dist.ctypes.data,
                                 prev_node.ctypes.data, prev_edge.ctypes.data, C.byref(st)))
+        return dist[:V], prev_node[:V], prev_edge[:V], st.as_dict()
+
+    def sssp_path_f64(self, cost, root=0, end=-1):
+        """sssp_path(G, dist, edge_cost, root, end, prev_node, prev_edge) of sssp_path_adj.gm: cost[E] float64 >= 0 by uploaded
+        forward edge slot, end = -1 for no target -- returns (dist[float64] with DBL_MAX for the unreached, prev_node[int32],
+        prev_edge[int32] as uploaded slots, stats), the bytes of the reference's loop run by one thread."""
+        cost = np.ascontiguousarray(cost, np.float64)
+        if cost.shape != (self.E,):
+            raise ValueError("cost must have one entry per edge")
+        V = self.V
+        dist = np.zeros(max(V, 1), np.float64)
+        prev_node, prev_edge = (np.zeros(max(V, 1), np.int32) for _ in range(2))
+        st = Stats()
+        _ck(lib().gmx_sssp_path_f64(self._h, int(root), int(end), cost.ctypes.data if self.E else None, dist.ctypes.data,
+                                    prev_node.ctypes.data, prev_edge.ctypes.data, C.byref(st)))
         return dist[:V], prev_node[:V], prev_edge[:V], st.as_dict()
 
     def scc(self):

@@ -95,8 +95,8 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
- *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len and gmx_v_cover's select are indexed by the stored slots);
+ *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_sssp_path_f64 and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge and gmx_v_cover's select are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
  *     gm_common_neighbor_iter.h): GMX_ERR_STATE when the forward rows are not sorted.  With sorted forward rows and an
@@ -254,6 +254,50 @@ int gmx_sssp(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host, int32_t* 
  * GMX_SSSP_PATH_SCHEDULE = round | nearfar picks the schedule (DESIGN.md 4.2b'); the results do not depend on it. */
 int gmx_sssp_path(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host /* [E] */, int32_t* dist_host /* [V] */,
                   gmx_node_t* prev_node_host /* [V] */, gmx_edge_t* prev_edge_host /* [V] or NULL */, gmx_stats_t* stats);
+
+/* sssp_path(G, dist, edge_cost, root, end, prev_node, prev_edge) of apps/src/sssp_path_adj.gm:1-33 (driver
+ * apps/output_cpp/src/sssp_path_adj_main.cc:107): a route query from root to end with Double edge costs, a predecessor node
+ * and a predecessor edge per vertex, pruned against the best distance to end found so far.  The program, per round:
+ *     B = dist[end] as the round finds it (DBL_MAX, the emitted +INF, while end is unreached; always, with end = -1);
+ *     every n with updated[n] && dist[n] < B, every out-slot e = n -> s: c = dist[n] + cost[e];
+ *         if (c < B && dist_nxt[s] > c) { dist_nxt[s] = c; updated_nxt[s] = true; prev_node[s] = n; prev_edge[s] = e; }
+ *     then dist = dist_nxt, updated = updated_nxt, updated_nxt = false; the loop ends when nothing is updated.
+ * B is a round's value, so what a vertex at or beyond end's distance ends up with depends on the rounds (it may keep a
+ * distance that is not its shortest): an asynchronous schedule computes something else there.  The device keeps the
+ * synchronous rounds, and with them the whole output is deterministic:
+ *   dist_host[V], prev_node_host[V], prev_edge_host[V] (the last may be NULL) are BYTE-IDENTICAL to what the loop above
+ *   gives when ONE thread runs it on the graph as uploaded (vertices ascending, a row in uploaded slot order), on every
+ *   vertex and for every upload form: per round a vertex whose dist_nxt dropped takes the minimum of the round's offers and,
+ *   among the offers equal to it, the one of the smallest UPLOADED slot; a vertex that did not drop keeps its predecessor.
+ *   prev_edge is an uploaded forward slot.  Unreached: DBL_MAX, -1, -1.  The root keeps 0, -1, -1 (costs are >= 0).
+ * Note that this is not gmx_sssp_path's rule (the smallest tight in-edge overall): the winner is the smallest slot among
+ * the offers of the round in which the final distance arrived.
+ * cost_host[E] is indexed like gmx_sssp's len, by the UPLOADED forward slots (through e_idx2idx when the upload sorted the
+ * rows).  Every cost must satisfy cost >= 0, checked on the device copy before the traversal: a negative cost or a NaN gives
+ * GMX_ERR_ARG and gmx_last_error() names the first offending slot; nothing is written.  -0.0 passes (sums start from +0.0,
+ * so no distance is ever -0.0); +inf passes and is never offered.  The one operation is dist[n] + cost[e] in double.
+ * end = -1 (gm_graph::NIL_NODE): no target, the bound stays DBL_MAX and the call is a double-cost sssp_path over the whole
+ * graph; any other end outside [0, V): GMX_ERR_ARG.  A root outside [0, V): DBL_MAX everywhere, -1 predecessors, GMX_OK
+ * (gmx_sssp_path's convention).  g, dist_host or prev_node_host NULL: GMX_ERR_ARG.  V = 0: GMX_OK.  E = 0: cost_host may
+ * be NULL.  Only the forward CSR is read (a GMX_GRAPH_NO_REVERSE graph works), rows in any order.
+ * The per-vertex words, the lists and the device copies of cost are kept on the graph for the next call (24 V + 20 V + 8 E
+ * bytes, 16 E when the upload sorted the rows) and freed with it; every call initialises what it reads.
+ * A round is three launches over lists (offers and winners over the rows of the queue, commit over the vertices that
+ * dropped; gmx_sssp_f64.hip, DESIGN.md 4.2b'').  Read at every call, the result does not depend on them:
+ *   GMX_SSSP_F64_TAIL   while the queued rows hold at most this many slots one workgroup runs the rounds in one launch,
+ *                       handing back to the grid when the queue outgrows it (0: never; huge: always; default 4096),
+ *   GMX_SSSP_F64_LOG=1  one stderr line per call: V, E, root, end, the threshold, rounds (grid + tail, tail launches),
+ *                       queue entries, slots, ms (2: before it a line per grid round and per tail launch).
+ * stats: iterations = rounds of the loop in which some vertex was updated (0 for a root out of range), edges_examined = row
+ * slots walked by the offer pass (the rows of the updated vertices below the bound), vertices_reached = updated vertices
+ * summed over the rounds (the root's included).  The reference also visits the root a second time in round 2 (updated_nxt
+ * starts as a copy of updated), where it offers what it offered in round 1 and nothing changes: that visit is neither run
+ * nor counted.  kernel_ms = device time from the first to the last launch, h2d_ms = upload
+ * and check of cost, d2h_ms = download of the three arrays. */
+int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end,
+                      const double* cost_host /* [E] */, double* dist_host /* [V] */,
+                      gmx_node_t* prev_node_host /* [V] */, gmx_edge_t* prev_edge_host /* [V] or NULL */,
+                      gmx_stats_t* stats);
 
 /* avg_teen_cnt(G, age, teen_cnt, K) (apps/src/avg_teen_cnt.gm; driver avg_teen_cnt_main.cc:24) and
  * conduct(G, member, num) (apps/src/conduct.gm; driver conduct_main.cc:45): count-reductions over neighbours
