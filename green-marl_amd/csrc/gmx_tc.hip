@@ -516,7 +516,8 @@ static int tc_count_part(gmx_graph_t* g, int part, int nparts, bool common_nbr_f
     const int64_t deal = (int64_t) 1 << TC_DEAL_SHIFT;
     const int64_t nblocks = (g->E + deal - 1) / deal;
     const int64_t nlocal = ((nblocks - part + nparts - 1) / nparts) * deal;
-    if (nlocal <= 0) return GMX_OK;
+    const bool staged = oriented && tc_use_lds();   // the staged-list kernel deals its work items, not these slot blocks
+    if (nlocal <= 0 && !staged) return GMX_OK;
     dbuf<unsigned long long> ctr;   // [0] total, [1] nbig
     GMX_CHECK(ctr.alloc(2));
     GMX_HIP(hipMemset(ctr.p, 0, 2 * sizeof(unsigned long long)));
@@ -525,7 +526,7 @@ static int tc_count_part(gmx_graph_t* g, int part, int nparts, bool common_nbr_f
     GMX_CHECK(ev1.create());
     GMX_HIP(hipEventRecord(ev0, 0));
     int64_t blocks = (nlocal + TC_THREADS - 1) / TC_THREADS;
-    if (oriented && tc_use_lds()) {
+    if (staged) {
         hipLaunchKernelGGL(tc_oriented_kernel, dim3(256 * 8), dim3(TCO_WAVES * 64), 0, 0, g->begin.p, g->node_idx.p,
                            (const int32_t*) g->r_begin.p, (const int32_t*) g->r_node_idx.p, g->V, part, nparts,
                            getenv("GMX_TC_ALONE") ? atoi(getenv("GMX_TC_ALONE")) : TCO_ALONE, getenv("GMX_TC_RATIO") ? atoi(getenv("GMX_TC_RATIO")) : TCO_RATIO, ctr.p + 1, ctr.p, (const uint32_t*) g->tc_hub_bits.p, g->V - g->tc_hubs, (int) (g->tc_hubs >> 5),
