@@ -395,6 +395,7 @@ void gmx_warm_modules() {
     gmx_touch_vcover();
     gmx_touch_match();
     gmx_touch_spf();
+    gmx_touch_route();
 }
 
 static int check_sizes(int64_t V, int64_t E) {

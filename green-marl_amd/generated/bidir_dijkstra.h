@@ -1,0 +1,23 @@
+// bidir_dijkstra.h -- entry points with the signatures gm_comp emits for apps/src/bidir_dijkstra.gm (call sites
+// apps/output_cpp/src/bidir_dijkstra_main.cc:37-42; E_P<Int> -> int32_t*, N_P<Node> -> node_t*, N_P<Edge> -> edge_t*,
+// Node in-arg -> node_t&, Node_Seq -> gm_node_seq&, Bool / Int results).  get_path is the one of sssp_dijkstra.gm too:
+// route_get_path.h declares it once for both headers.
+#ifndef GM_GENERATED_CPP_BIDIR_DIJKSTRA_H
+#define GM_GENERATED_CPP_BIDIR_DIJKSTRA_H
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <stdint.h>
+#include <float.h>
+#include <limits.h>
+#include <cmath>
+#include <algorithm>
+#include <omp.h>
+#include "gm.h"
+#include "route_get_path.h"
+
+bool bidir_dijkstra(gm_graph& G, int32_t* G_Weight,
+    node_t& src, node_t& dst,
+    node_t* G_Parent, edge_t* G_ParentEdge);
+
+#endif

@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -111,6 +111,10 @@ def lib():
         L.gmx_sssp.argtypes = [vp, i32, vp, vp, C.POINTER(Stats)]
         L.gmx_sssp_path.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(Stats)]
         L.gmx_sssp_path_f64.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.POINTER(Stats)]
+        L.gmx_route_create.argtypes = [vp, vp, C.POINTER(vp)]
+        L.gmx_route_free.argtypes = [vp]
+        L.gmx_route_query.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i64), vp, vp, i64, C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_bidir_dijkstra.argtypes = [vp, vp, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_scc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_communities.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_potential_friends.argtypes = [vp, i32, i32, vp, vp, i64, C.POINTER(i64), C.POINTER(Stats)]
@@ -213,6 +217,38 @@ def copy_bandwidth(nbytes=1 << 30, iters=10):
 
 def _i32(a):
     return np.ascontiguousarray(a, np.int32)
+
+
+class Route:
+    """gmx_route_t: the weights of Graph.route() on the device and the scratch of a query."""
+
+    def __init__(self, graph, handle):
+        self._g = graph          # borrowed: keeps the graph alive as long as the route
+        self._h = handle
+
+    def query(self, src, dst, cap=None):
+        """One pair -> (found, cost or None, path_node[int32], path_edge[int32], hops, stats): the vertices after src up to dst
+        and the uploaded forward slot of the edge into each; with cap < hops the first cap of them."""
+        if not self._h:
+            raise GmxError("route has been freed")
+        cap = self._g.V if cap is None else int(cap)
+        pn, pe = (np.zeros(max(cap, 1), np.int32) for _ in range(2))
+        found, cost, hops, st = C.c_int32(0), C.c_int64(0), C.c_int64(0), Stats()
+        _ck(lib().gmx_route_query(self._h, int(src), int(dst), C.byref(found), C.byref(cost), pn.ctypes.data, pe.ctypes.data, cap,
+                                  C.byref(hops), C.byref(st)))
+        k = min(hops.value, cap)
+        return bool(found.value), (cost.value if found.value else None), pn[:k], pe[:k], hops.value, st.as_dict()
+
+    def free(self):
+        if self._h:
+            lib().gmx_route_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class Graph:
@@ -371,6 +407,29 @@ class Graph:
         _ck(lib().gmx_sssp_path_f64(self._h, int(root), int(end), cost.ctypes.data if self.E else None, dist.ctypes.data,
                                     prev_node.ctypes.data, prev_edge.ctypes.data, C.byref(st)))
         return dist[:V], prev_node[:V], prev_edge[:V], st.as_dict()
+
+    def route(self, weight):
+        """gmx_route_create: weight[E] int32 >= 0 by uploaded forward edge slot -> Route, which keeps the weights on the device
+        and answers (src, dst) pairs.  It borrows this graph: free it first."""
+        weight = _i32(weight)
+        if weight.shape != (self.E,):
+            raise ValueError("weight must have one entry per edge")
+        h = C.c_void_p()
+        _ck(lib().gmx_route_create(self._h, weight.ctypes.data if self.E else None, C.byref(h)))
+        return Route(self, h)
+
+    def bidir_dijkstra(self, weight, src, dst):
+        """bidir_dijkstra(G, Weight, src, dst, Parent, ParentEdge): returns (found, parent[int32], parent_edge[int32], stats);
+        the parents are -1 off the returned route, parent_edge an uploaded forward slot."""
+        weight = _i32(weight)
+        if weight.shape != (self.E,):
+            raise ValueError("weight must have one entry per edge")
+        V = self.V
+        parent, parent_edge = (np.zeros(max(V, 1), np.int32) for _ in range(2))
+        found, st = C.c_int32(0), Stats()
+        _ck(lib().gmx_bidir_dijkstra(self._h, weight.ctypes.data if self.E else None, int(src), int(dst), parent.ctypes.data,
+                                     parent_edge.ctypes.data, C.byref(found), C.byref(st)))
+        return bool(found.value), parent[:V], parent_edge[:V], st.as_dict()
 
     def scc(self):
         """kosaraju(G, mem): strongly connected components -- returns (comp[int32], count, stats).  comp numbers the

@@ -95,8 +95,8 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_sssp_path_f64 and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
- *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge and gmx_v_cover's select are indexed by the stored slots);
+ *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge and gmx_v_cover's select are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
  *     gm_common_neighbor_iter.h): GMX_ERR_STATE when the forward rows are not sorted.  With sorted forward rows and an
@@ -298,6 +298,70 @@ int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end,
                       const double* cost_host /* [E] */, double* dist_host /* [V] */,
                       gmx_node_t* prev_node_host /* [V] */, gmx_edge_t* prev_edge_host /* [V] or NULL */,
                       gmx_stats_t* stats);
+
+/* ---- route queries with Int edge weights: bidir_dijkstra(G, Weight, src, dst, Parent, ParentEdge) of
+ * apps/src/bidir_dijkstra.gm and dijkstra(G, Len, root, dest, Parent, ParentEdge) of apps/src/sssp_dijkstra.gm (drivers
+ * apps/output_cpp/src/bidir_dijkstra_main.cc:37, sssp_dijkstra_main.cc:37) ----
+ * One source, one destination, one route back.  A search from src over out-edges and one from dst over in-edges run in
+ * turns, each round expanding the side whose queue holds fewer row slots, and stop when the two balls meet; on a graph
+ * without a reverse CSR (GMX_GRAPH_NO_REVERSE) the same code runs with the reverse side never expanded, which is
+ * sssp_dijkstra.gm's one-sided search with early exit.  The weights stay on the device in a route object, so that many
+ * pairs can be answered on one graph with one weight array (the drivers' pairs-file mode) without uploading it again.
+ *
+ * gmx_route_create: weight_host[E] is indexed like gmx_sssp's len, by the UPLOADED forward slots (through e_idx2idx when
+ * the upload sorted the rows).  Every weight must be >= 0 (zero is allowed), checked on the device copy before anything
+ * else: a negative one gives GMX_ERR_ARG, gmx_last_error() names the first offending slot, and no object is returned
+ * (*out = NULL).  Path sums must stay below INT_MAX (gmx_sssp's convention).  The object keeps on the device the weights by
+ * forward slot and, when the graph has a reverse CSR, by reverse slot, for each reverse slot the uploaded forward slot it
+ * stands for (the two CSRs' slots paired in the order of their (dst, src) keys: any row order works, the reverse CSR
+ * must be the transpose), and all per-vertex words and queues of a query: 12 E + 52 V bytes.  THE OBJECT BORROWS g: free
+ * it before the graph.  E = 0: weight_host may be NULL.  V = 0: GMX_OK (there is no vertex to query).
+ *
+ * gmx_route_query answers one pair and uploads nothing beyond a few scalars; every call initialises what it reads.
+ *   *found  1 iff dst is reachable from src over out-edges.  src == dst is found, with cost 0 and 0 hops.
+ *   *cost   the shortest distance: exact, whatever the knobs.  Left alone when not found.
+ *   *hops   the number of edges of the returned route (0 when not found).  path_node[k] is the k-th vertex AFTER src (the
+ *           last one is dst; get_path does not push the start either), path_edge[k] the UPLOADED forward slot of the edge
+ *           into path_node[k], also for the edges the reverse search walked.  Either array may be NULL.  With hops > cap
+ *           the first cap entries from the src end are written, *hops still reports the full length, and the call is GMX_OK.
+ *   The route: consecutive edges join up from src to dst, each path_edge lies in the row of its source and points at its
+ *   path_node, the weights sum to *cost, no vertex repeats (so it has fewer than V edges) -- with zero weights, zero-weight
+ *   cycles, parallel edges and self loops.  WHICH of several equally short routes is returned is NOT specified: it may
+ *   differ between runs and between knob settings.
+ *   src or dst outside [0, V), r, found, cost or hops NULL, cap < 0: GMX_ERR_ARG, nothing is written.
+ *
+ * gmx_bidir_dijkstra = create + query + free, what the drop-in entries call.  parent_host[V] / parent_edge_host[V] (the
+ * latter may be NULL) are -1 everywhere except on the vertices of the returned route other than src, where they hold the
+ * predecessor and its uploaded forward slot: get_path(src, dst) walks exactly that route.  Not found: all -1, *found = 0.
+ *
+ * Not reproduced from the reference (its frontier is gm_mutatable_priority_map_unordered_min, whose order among equal
+ * keys is an accident of a heap, so there is no one-thread run to match):
+ *   - bidir_dijkstra.gm leaves the residue of both searches in Parent and never initialises ParentEdge off the route;
+ *     here both are -1 off the route;
+ *   - for src == dst, bidir_dijkstra.gm reports a cycle through src, or False when there is none; here: found, cost 0,
+ *     0 hops, all parents -1.
+ *
+ * Knobs, read at every call; the flag and the cost do not depend on them:
+ *   GMX_ROUTE_SIDES=both|forward  forward: never expand the reverse side (default both when a reverse CSR exists);
+ *   GMX_ROUTE_TAIL=<slots>        while the side to expand holds at most this many slots one workgroup runs the rounds of
+ *                                 both sides in one launch, handing back to the grid when a queue outgrows it (0: never;
+ *                                 huge: always; default 4096);
+ *   GMX_ROUTE_LOG=1               one stderr line per query:
+ *     gmx route: V <V> E <E> src <s> dst <d> sides <both|forward>; tail <slots>; rounds F <n> grid + <n> tail, R <n> grid + <n> tail
+ *     in <n> launches; slots F <n> R <n>; queued <n>; found <0|1> cost <c> meet <v> hops <h>; ms <t>
+ * stats: iterations = rounds, both sides counted; edges_examined = row slots walked, both sides counted; vertices_reached
+ * = queue entries (the two seeds included); kernel_ms = device time from the first launch to the route's extraction, d2h_ms
+ * = download of the route; h2d_ms = upload, check and gathers of the weights, filled by gmx_bidir_dijkstra only (a query
+ * uploads nothing).  Design and the argument for the stop rule: DESIGN.md 4.2b'''. */
+typedef struct gmx_route gmx_route_t;
+int gmx_route_create(gmx_graph_t* g, const int32_t* weight_host /* [E] */, gmx_route_t** out);
+int gmx_route_free(gmx_route_t* r);
+int gmx_route_query(gmx_route_t* r, gmx_node_t src, gmx_node_t dst, int32_t* found, int64_t* cost,
+                    gmx_node_t* path_node /* [cap] or NULL */, gmx_edge_t* path_edge /* [cap] or NULL */,
+                    int64_t cap, int64_t* hops, gmx_stats_t* stats);
+int gmx_bidir_dijkstra(gmx_graph_t* g, const int32_t* weight_host /* [E] */, gmx_node_t src, gmx_node_t dst,
+                       gmx_node_t* parent_host /* [V] */, gmx_edge_t* parent_edge_host /* [V] or NULL */,
+                       int32_t* found, gmx_stats_t* stats);
 
 /* avg_teen_cnt(G, age, teen_cnt, K) (apps/src/avg_teen_cnt.gm; driver avg_teen_cnt_main.cc:24) and
  * conduct(G, member, num) (apps/src/conduct.gm; driver conduct_main.cc:45): count-reductions over neighbours
