@@ -314,13 +314,6 @@ bcb_accumulate_kernel(const uint32_t* __restrict__ lvl, const float2* __restrict
 }
 
 // ---------------------------------------------------------------- host side
-static int64_t bcb_env(const char* name, int64_t dflt, int64_t lo, int64_t hi) {
-    const char* e = getenv(name);
-    if (!e || !*e) return dflt;
-    const long long v = atoll(e);
-    return v < lo ? lo : (v > hi ? hi : (int64_t) v);
-}
-
 // device bytes of a batch of width W on V vertices: sd 8, lvl 1 and the staged levels 1 per (vertex, column); two row lists,
 // minmax and a little padding per vertex (the rule include/gmx.h states for GMX_BCB_MEM_MB)
 static size_t bcb_bytes(int64_t V, int W) { return (size_t) V * (10 * (size_t) W + 10) + 4096 * (size_t) W; }
@@ -453,19 +446,19 @@ extern "C" int gmx_bc_batch(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nse
     if (V == 0) return GMX_OK;
     for (int32_t i = 0; i < nseeds; i++) GMX_REQUIRE(seeds[i] >= 0 && seeds[i] < V, "seed %d out of range", seeds[i]);
     bcb_knobs kn;
-    kn.max_depth = (int32_t) bcb_env("GMX_BCB_MAX_DEPTH", BCB_DEPTH_CAP, 0, BCB_DEPTH_CAP);   // (the environment lowers it, never raises it)
-    kn.long_min = (int32_t) bcb_env("GMX_BCB_LONG_MIN", 256, 1, INT_MAX);
-    kn.trace = bcb_env("GMX_BCB_TRACE", 0, 0, 1) != 0;
+    kn.max_depth = (int32_t) gmx_env_int("GMX_BCB_MAX_DEPTH", BCB_DEPTH_CAP, 0, BCB_DEPTH_CAP);   // (the environment lowers it, never raises it)
+    kn.long_min = (int32_t) gmx_env_int("GMX_BCB_LONG_MIN", 256, 1, INT_MAX);
+    kn.trace = gmx_env_int("GMX_BCB_TRACE", 0, 0, 1) != 0;
     int W = width;
     if (W == 0) {
-        W = (int) bcb_env("GMX_BCB_WIDTH", BCB_DEFAULT_WIDTH, 0, 1 << 20);
+        W = (int) gmx_env_int("GMX_BCB_WIDTH", BCB_DEFAULT_WIDTH, 0, 1 << 20);
         GMX_REQUIRE(W == 1 || W == 16 || W == 32 || W == 64, "GMX_BCB_WIDTH=%d: 1, 16, 32 or 64", W);
         while (W > 16 && W / 2 >= nseeds) W /= 2;   // (no wider than the seeds need)
     }
     if (W > 1) {   // a batch has to fit: halve the width down to 16, then the per-seed path
         size_t free_b = 0, total_b = 0;
         GMX_HIP(hipMemGetInfo(&free_b, &total_b));
-        const int64_t cap_mb = bcb_env("GMX_BCB_MEM_MB", -1, 0, INT64_MAX >> 20);
+        const int64_t cap_mb = gmx_env_int("GMX_BCB_MEM_MB", -1, 0, INT64_MAX >> 20);
         const size_t room = cap_mb >= 0 && (size_t) cap_mb << 20 < free_b ? (size_t) cap_mb << 20 : free_b;
         while (W >= 16 && bcb_bytes(V, W) > room) W /= 2;
         if (W < 16) W = 1;

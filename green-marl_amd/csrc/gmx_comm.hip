@@ -581,12 +581,6 @@ __global__ void comm_close_kernel(comm_arrays a, comm_rec* rec) {
 }
 
 // ---------------------------------------------------------------- host
-static int64_t comm_env(const char* name, int64_t dflt, int64_t lo, int64_t hi) {
-    const char* e = getenv(name);
-    if (!e || !*e) return dflt;
-    const long long v = atoll(e);
-    return v < lo ? lo : (v > hi ? hi : (int64_t) v);
-}
 static int comm_grid(int64_t items_per_block_work, int max_blocks) {
     return (int) (items_per_block_work < 1 ? 1 : (items_per_block_work > max_blocks ? max_blocks : items_per_block_work));
 }
@@ -607,13 +601,13 @@ extern "C" int gmx_communities(gmx_graph_t* g, int32_t max_rounds, gmx_node_t* c
         return GMX_OK;
     }
     // thresholds, read at every call: rows of fewer than WAVE_MIN slots are short, of BLOCK_MIN or more hubs
-    const int32_t wave_min = (int32_t) comm_env("GMX_COMM_WAVE_MIN", COMM_WAVE_MIN, 1, INT32_MAX);
-    const int32_t block_min = (int32_t) comm_env("GMX_COMM_BLOCK_MIN", COMM_BLOCK_MIN, 1, INT32_MAX);
+    const int32_t wave_min = (int32_t) gmx_env_int("GMX_COMM_WAVE_MIN", COMM_WAVE_MIN, 1, INT32_MAX);
+    const int32_t block_min = (int32_t) gmx_env_int("GMX_COMM_BLOCK_MIN", COMM_BLOCK_MIN, 1, INT32_MAX);
     int32_t cap = COMM_LDS_SLOTS_MIN;   // the power of two at or below the request
-    const int64_t want = comm_env("GMX_COMM_LDS_SLOTS", COMM_LDS_SLOTS, COMM_LDS_SLOTS_MIN, COMM_LDS_SLOTS_MAX);
+    const int64_t want = gmx_env_int("GMX_COMM_LDS_SLOTS", COMM_LDS_SLOTS, COMM_LDS_SLOTS_MIN, COMM_LDS_SLOTS_MAX);
     while ((int64_t) cap * 2 <= want) cap *= 2;
     const int32_t wcap = cap / COMM_WAVE_SHARE;
-    const bool worklist = g->has_reverse && comm_env("GMX_COMM_WORKLIST", 1, 0, 1) != 0;
+    const bool worklist = g->has_reverse && gmx_env_int("GMX_COMM_WORKLIST", 1, 0, 1) != 0;
     const bool round_log = getenv("GMX_COMM_ROUNDS") != nullptr;   // per-round line for tools/comm_prof.py
     const size_t wave_lds = (size_t) (COMM_THREADS / 64) * (2 * (size_t) wcap + 2 * COMM_STAGE + 4) * sizeof(int32_t);
     const size_t block_lds = 2 * (size_t) cap * sizeof(int32_t);

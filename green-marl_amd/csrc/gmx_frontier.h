@@ -6,6 +6,10 @@
 // its two diagonals (frontier_tile_search / frontier_tile_split), stages the rows it touches in LDS (frontier_stage),
 // finds the row of each of its edges there (frontier_slot), appends what it discovers to an LDS list with one ballot per
 // wave (wave_append) and claims the queue tail once (frontier_flush).
+//
+// Next to the tile, what the round kernels built on it share: the 64-lane reductions (wave_sum / wave_min / wave_max), the
+// row of a slot (csr_row_of), the walk of a short queue by one workgroup (tail_rows) and the kernels that stage an edge
+// property (gather_by_order_kernel, first_bad_slot_kernel).
 #ifndef GMX_FRONTIER_H_
 #define GMX_FRONTIER_H_
 
@@ -170,6 +174,103 @@ __device__ __forceinline__ void frontier_flush(const int32_t* s_list, unsigned i
 __device__ __forceinline__ void frontier_flush(const int32_t* s_list, unsigned int cnt, unsigned long long* tail, int32_t* __restrict__ q,
                                                unsigned long long* s_base) {
     frontier_flush(s_list, cnt, tail, q, s_base, [] {});
+}
+
+// ---- 64-lane reductions (T: a 32- or 64-bit word); every lane of the wave must be here, the result is in lane 0
+template <class T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+    return x;
+}
+template <class T>
+__device__ __forceinline__ T wave_min(T x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const T y = __shfl_down(x, o, 64);
+        x = y < x ? y : x;
+    }
+    return x;
+}
+template <class T>
+__device__ __forceinline__ T wave_max(T x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const T y = __shfl_down(x, o, 64);
+        x = y > x ? y : x;
+    }
+    return x;
+}
+
+// the row that holds slot e: the last row that starts at or before it (the empty rows before it start there too)
+__device__ __forceinline__ int32_t csr_row_of(const int32_t* __restrict__ begin, int64_t V, uint32_t e) {
+    int64_t lo = 0, hi = V - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if ((uint32_t) begin[mid] <= e) lo = mid; else hi = mid - 1;
+    }
+    return (int32_t) lo;
+}
+
+// ---- the tail walk: the rows of a short queue la[0 .. n) by the waves of ONE workgroup (wave `wave` of `nwaves`, all of
+// them here with the same n), 64 rows at a time, a lane per row.  load(have, v, deg) -> P is called by every lane once per
+// 64 rows (have: the lane has row v of deg slots) and returns what the row's slots need besides their index.
+// slot(on, P, e) is called by the WHOLE wave at every step -- it may ballot, as wave_append does -- with on false in the
+// lanes that have no slot e:
+//   - a row of at most LANE_MAX slots is walked by its lane: step k takes slot k of every such row, and the loop ends at the
+//     first k no lane has a slot for, which the ballot makes the same k in all 64 lanes;
+//   - a longer row is walked by the wave, 64 slots a step: its bounds and P come from its lane by __shfl, so the trip count
+//     is wave-uniform again.
+// Nothing orders the slots of different rows; the caller puts its barrier behind the walk.
+template <int LANE_MAX, class Load, class Slot>
+__device__ __forceinline__ void tail_rows(const int32_t* la, int64_t n, const int32_t* begin, int lane, int64_t wave, int64_t nwaves, Load load,
+                                          Slot slot) {
+    for (int64_t base = wave * 64; base < n; base += nwaves * 64) {
+        const bool have = base + lane < n;
+        const int32_t v = have ? la[base + lane] : 0;
+        const int32_t b = have ? begin[v] : 0, e = have ? begin[v + 1] : 0;
+        const auto p = load(have, v, e - b);
+        const bool by_wave = e - b > LANE_MAX;
+        for (int32_t k = 0; k < LANE_MAX; k++) {
+            const bool on = !by_wave && b + k < e;
+            if (!__ballot(on)) break;   // (wave-uniform)
+            slot(on, p, b + k);
+        }
+        unsigned long long lm = __ballot(by_wave);
+        while (lm) {
+            const int src = __builtin_ctzll(lm);
+            lm &= lm - 1;
+            const int32_t wb = __shfl(b, src, 64), we = __shfl(e, src, 64);
+            const auto wp = __shfl(p, src, 64);
+            for (int32_t x = wb; x < we; x += 64) slot(x + lane < we, wp, x + lane);
+        }
+    }
+}
+
+// ---- an edge property on its way to the device's slots
+// dst[i] = src[order[i]]: a property given by uploaded slot brought into the order of the sorted rows; a slot map composed
+template <class T>
+__global__ void gather_by_order_kernel(const T* __restrict__ src, const int32_t* __restrict__ order, int64_t n, T* __restrict__ dst) {
+    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (; i < n; i += stride) dst[i] = src[order[i]];
+}
+
+// out->bad = E - (the first slot i with !(x[i] >= 0): negative or, for a double, not a number; -0.0 passes), 0: none.
+// Ctl: the caller's control block, bad an unsigned 64-bit word of it that starts at 0.  Launched with the unit's own block
+// size, which must not exceed BFS_THREADS (the units assert that theirs equals it).
+template <class T, class Ctl>
+__global__ void __launch_bounds__(BFS_THREADS) first_bad_slot_kernel(const T* __restrict__ x, int64_t E, Ctl* __restrict__ out) {
+    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    unsigned long long worst = 0;
+    for (; i < E; i += stride)
+        if (!(x[i] >= 0)) {
+            const unsigned long long w = (unsigned long long) (E - i);
+            worst = w > worst ? w : worst;
+        }
+    worst = wave_max(worst);
+    if ((threadIdx.x & 63) == 0 && worst) atomicMax(&out->bad, worst);
 }
 
 #endif

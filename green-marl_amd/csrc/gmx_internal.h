@@ -96,6 +96,21 @@ struct gmx_pinned {
         return GMX_OK;
     }
 };
+// a device control block (count words of it) into its pinned mirror on stream 0; synchronises
+template <typename T>
+static inline int gmx_read_back(gmx_pinned<T>& host, const T* dev, size_t count = 1) {
+    GMX_HIP(hipMemcpyAsync(host.p, dev, count * sizeof(T), hipMemcpyDeviceToHost, 0));
+    GMX_HIP(hipStreamSynchronize(0));
+    return GMX_OK;
+}
+
+// an integer knob of the environment: dflt when unset or empty, else clamped to [lo, hi]
+static inline int64_t gmx_env_int(const char* name, int64_t dflt, int64_t lo, int64_t hi) {
+    const char* e = getenv(name);
+    if (!e || !*e) return dflt;
+    const long long v = atoll(e);
+    return v < lo ? lo : (v > hi ? hi : (int64_t) v);
+}
 
 // ---- workspace: where the big temporaries of graph construction and plan builds live ----
 // Device memory that has just been freed is not free: the driver wipes it before it hands it out again, and a
@@ -209,6 +224,9 @@ int gmx_keys_from_csr(const int32_t* begin, const int32_t* idx, int64_t V, int64
                       bool transpose, const int32_t* perm, uint64_t* keys, hipStream_t stream);
 int gmx_keys_from_edges(const int32_t* src, const int32_t* dst, int64_t E, bool transpose,
                         const int32_t* perm, uint64_t* keys, hipStream_t stream);
+// a[i] = i: the values a sort of keys carries along.  Defined in gmx_graph.hip and launched from gmx_route.hip as well: without
+// relocatable device code that works through the defining unit's host stub, so the kernel must stay non-static there.
+__global__ void iota_kernel(int32_t* __restrict__ a, int64_t n);
 
 // ---- cold-source part of the PageRank sweep (gmx_pr_cold.hip) ----
 // Sources whose id inside their rank range [r * slice, (r + 1) * slice) is >= T are "cold": their edges are not

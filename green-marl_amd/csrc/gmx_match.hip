@@ -65,11 +65,6 @@ __device__ __forceinline__ rbm_word rbm_load(const rbm_word* p) { return __hip_a
 __device__ __forceinline__ void rbm_max(rbm_word* p, rbm_word key) {
     if (rbm_load(p) < key) atomicMax(p, key);
 }
-__device__ __forceinline__ rbm_word rbm_wave_sum(rbm_word x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;   // (lane 0)
-}
 
 // ------------------------------------------------------------------ round pieces (shared by the grid kernels and the tail)
 // Slot (n, t) of a live left, whole wave here; on: the lane has one.  Returns whether it is a proposal.
@@ -157,8 +152,8 @@ __global__ void __launch_bounds__(RBM_THREADS) rbm_init_kernel(rbm_state S, int3
         }
         wave_append(keep, (int32_t) v, s_win, &s_nwin, lane);
     }
-    deg = rbm_wave_sum(deg);
-    lefts = rbm_wave_sum(lefts);
+    deg = wave_sum(deg);
+    lefts = wave_sum(lefts);
     if (lane == 0) {
         if (deg) atomicAdd(&s_deg, deg);
         if (lefts) atomicAdd(&s_lefts, lefts);
@@ -202,7 +197,7 @@ __global__ void __launch_bounds__(BFS_THREADS) rbm_propose_kernel(rbm_state S, c
         props += prop ? 1 : 0;
         rbm_propose(S, prop, nn, tt, r, lane, s_win, &s_nwin);
     }
-    props = rbm_wave_sum(props);
+    props = wave_sum(props);
     if (lane == 0 && props) atomicAdd(&s_prop, props);
     __syncthreads();
     frontier_flush(s_win, s_nwin, &S.ctr->ntouch, S.touched, &s_base, [&] {
@@ -244,8 +239,8 @@ __global__ void __launch_bounds__(RBM_THREADS) rbm_commit_kernel(rbm_state S, co
         if (what == 2) deg += (rbm_word) (S.begin[v + 1] - S.begin[v]);
         wave_append(what == 2, v, s_win, &s_nwin, lane);
     }
-    deg = rbm_wave_sum(deg);
-    matched = rbm_wave_sum(matched);
+    deg = wave_sum(deg);
+    matched = wave_sum(matched);
     if (lane == 0) {
         if (deg) atomicAdd(&s_deg, deg);
         if (matched) atomicAdd(&s_match, matched);
@@ -261,6 +256,7 @@ __global__ void __launch_bounds__(RBM_THREADS) rbm_commit_kernel(rbm_state S, co
 // la[0 .. n): the live lefts of round r (first: no round has run).  Words that atomics
 // write (suitor, reply) are read back with device-scope loads behind the workgroup's barrier; Match, the proposal stamps
 // and the lists are plain stores of this workgroup, visible to its waves behind the same barrier, as in gmx_vcover.hip.
+// The rows are walked by tail_rows (gmx_frontier.h).
 // At most V rounds (every round but the last matches a pair), each a bounded loop: no waiting on anybody.
 __global__ void __launch_bounds__(RBM_TAIL_THREADS) rbm_tail_kernel(rbm_state S, int32_t* la, int32_t* lb, int64_t n, int first, int32_t r) {
     __shared__ unsigned int s_ntouch, s_nnext;
@@ -278,32 +274,18 @@ __global__ void __launch_bounds__(RBM_TAIL_THREADS) rbm_tail_kernel(rbm_state S,
     while (n > 0) {
         rbm_word props = 0;
         const auto match_of = [&](int32_t u) { return S.match[u]; };
-        const auto slot = [&](bool on, int32_t v, int32_t idx) {   // whole wave
+        const auto slot = [&](bool on, int32_t v, int32_t idx) {
             const int32_t tt = on ? S.node_idx[idx] : 0;
             const bool prop = first ? rbm_is_proposal<true>(S, on, v, tt, match_of) : rbm_is_proposal<false>(S, on, v, tt, match_of);
             props += prop ? 1 : 0;
             rbm_propose(S, prop, v, tt, r, lane, S.touched, &s_ntouch);
         };
-        for (int64_t base = wave * 64; base < n; base += nwaves * 64) {   // 64 rows: a lane each, the long ones by the wave
-            const bool have = base + lane < n;
-            const int32_t v = have ? la[base + lane] : 0;
-            const int32_t b = have ? S.begin[v] : 0, e = have ? S.begin[v + 1] : 0;
-            slots += (rbm_word) (e - b);
-            const bool by_wave = e - b > RBM_TAIL_LANE;
-            for (int32_t k = 0; k < RBM_TAIL_LANE; k++) {
-                const bool on = !by_wave && b + k < e;
-                if (!__ballot(on)) break;   // (wave-uniform)
-                slot(on, v, b + k);
-            }
-            unsigned long long lm = __ballot(by_wave);
-            while (lm) {
-                const int src = __builtin_ctzll(lm);
-                lm &= lm - 1;
-                const int32_t wv = __shfl(v, src, 64), wb = __shfl(b, src, 64), we = __shfl(e, src, 64);
-                for (int32_t x = wb; x < we; x += 64) slot(x + lane < we, wv, x + lane);
-            }
-        }
-        props = rbm_wave_sum(props);
+        const auto load = [&](bool, int32_t v, int32_t deg) {
+            slots += (rbm_word) deg;
+            return v;
+        };
+        tail_rows<RBM_TAIL_LANE>(la, n, S.begin, lane, wave, nwaves, load, slot);
+        props = wave_sum(props);
         if (lane == 0 && props) atomicAdd(&s_prop, props);
         __syncthreads();
         const rbm_word total = s_prop;
@@ -336,8 +318,8 @@ __global__ void __launch_bounds__(RBM_TAIL_THREADS) rbm_tail_kernel(rbm_state S,
         r++;
         __syncthreads();
     }
-    slots = rbm_wave_sum(slots);
-    matched = rbm_wave_sum(matched);
+    slots = wave_sum(slots);
+    matched = wave_sum(matched);
     if (lane == 0) {
         const int sh = (int) wave & (RBM_SHARDS - 1);
         if (slots) atomicAdd(&S.ctr->shard[sh].tail_slots, slots);
@@ -350,13 +332,6 @@ __global__ void __launch_bounds__(RBM_TAIL_THREADS) rbm_tail_kernel(rbm_state S,
 }
 
 // ------------------------------------------------------------------ host
-static int64_t rbm_env(const char* name, int64_t dflt) {
-    const char* e = getenv(name);
-    if (!e || !*e) return dflt;
-    const long long v = atoll(e);
-    return v < 0 ? 0 : (v > INT32_MAX ? INT32_MAX : v);
-}
-
 struct rbm_totals {
     rbm_word proposals = 0, matched = 0, lefts = 0, tail_slots = 0;
 };
@@ -378,8 +353,8 @@ extern "C" int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_l
     *count = 0;
     const int64_t V = g->V, E = g->E;
     if (V == 0) return GMX_OK;
-    const int64_t tail_from = rbm_env("GMX_RBM_TAIL", RBM_TAIL);   // read at every call; the result does not depend on it
-    const int64_t log = rbm_env("GMX_RBM_LOG", 0);                 // 1: one line per call; 2: a line per grid round before it
+    const int64_t tail_from = gmx_env_int("GMX_RBM_TAIL", RBM_TAIL, 0, INT32_MAX);   // read at every call; the result does not depend on it
+    const int64_t log = gmx_env_int("GMX_RBM_LOG", 0, 0, INT32_MAX);                 // 1: one line per call; 2: a line per grid round before it
 
     dbuf<uint8_t> is_left;
     dbuf<int32_t> match, prop_round, touched, l0, l1;
@@ -413,11 +388,6 @@ extern "C" int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_l
     S.ctr = ctr.p;
     S.V = V;
     rbm_counters* h = h_ctr.p;
-    auto read_ctr = [&]() -> int {   // synchronises
-        GMX_HIP(hipMemcpyAsync(h, ctr.p, sizeof(rbm_counters), hipMemcpyDeviceToHost, 0));
-        GMX_HIP(hipStreamSynchronize(0));
-        return GMX_OK;
-    };
 
     GMX_HIP(hipEventRecord(ev[0], 0));
     GMX_HIP(hipMemcpyAsync(is_left.p, is_left_host, (size_t) V, hipMemcpyHostToDevice, 0));
@@ -433,7 +403,7 @@ extern "C" int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_l
     int32_t* lb = l1.p;
     hipLaunchKernelGGL(rbm_init_kernel, dim3((unsigned) ((V + RBM_CHUNK - 1) / RBM_CHUNK)), dim3(RBM_THREADS), 0, 0, S, la);
     GMX_HIP(hipGetLastError());
-    GMX_CHECK(read_ctr());
+    GMX_CHECK(gmx_read_back(h_ctr, ctr.p));
     int64_t n = (int64_t) h->nlive, m = (int64_t) h->mlive;
     const int64_t lefts = (int64_t) rbm_sum(*h).lefts;
     int32_t round = 0, tail_rounds = 0;
@@ -445,7 +415,7 @@ extern "C" int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_l
             const double t_tail0 = gmx_tick::now();
             hipLaunchKernelGGL(rbm_tail_kernel, dim3(1), dim3(RBM_TAIL_THREADS), 0, 0, S, la, lb, n, round == 0 ? 1 : 0, round + 1);
             GMX_HIP(hipGetLastError());
-            GMX_CHECK(read_ctr());
+            GMX_CHECK(gmx_read_back(h_ctr, ctr.p));
             tail_rounds = (int32_t) h->tail_rounds;
             tail_ms = (gmx_tick::now() - t_tail0) * 1e3;
             break;
@@ -461,7 +431,7 @@ extern "C" int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_l
         hipLaunchKernelGGL(rbm_reply_kernel, dim3(grid_for(m < V ? m : V, RBM_THREADS)), dim3(RBM_THREADS), 0, 0, S, round + 1);   // a slot touches at most one right
         hipLaunchKernelGGL(rbm_commit_kernel, dim3((unsigned) ((n + RBM_CHUNK - 1) / RBM_CHUNK)), dim3(RBM_THREADS), 0, 0, S, (const int32_t*) la, n, round + 1, lb);
         GMX_HIP(hipGetLastError());
-        GMX_CHECK(read_ctr());
+        GMX_CHECK(gmx_read_back(h_ctr, ctr.p));
         grid_slots += m;
         const rbm_word p = rbm_sum(*h).proposals;
         if (log >= 2)

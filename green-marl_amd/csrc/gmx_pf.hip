@@ -379,12 +379,6 @@ __global__ void __launch_bounds__(PF_THREADS) pf_bitmap_kernel(pf_arrays a, cons
 }
 
 // ---------------------------------------------------------------- host
-static int64_t pf_env(const char* name, int64_t dflt, int64_t lo, int64_t hi) {
-    const char* e = getenv(name);
-    if (!e || !*e) return dflt;
-    const long long v = atoll(e);
-    return v < lo ? lo : (v > hi ? hi : (int64_t) v);
-}
 static int pf_grid(int64_t want, int max_blocks) { return (int) (want < 1 ? 1 : (want > max_blocks ? max_blocks : want)); }
 
 struct pf_plan {
@@ -464,15 +458,15 @@ extern "C" int gmx_potential_friends(gmx_graph_t* g, gmx_node_t v_lo, gmx_node_t
 
     // knobs, read at every call; the results do not depend on them
     pf_plan P{};
-    P.wave_max = pf_env("GMX_PF_WAVE_MAX", PF_WAVE_MAX, 0, INT64_MAX);
-    P.block_max = pf_env("GMX_PF_BLOCK_MAX", PF_BLOCK_MAX, 0, INT64_MAX);
+    P.wave_max = gmx_env_int("GMX_PF_WAVE_MAX", PF_WAVE_MAX, 0, INT64_MAX);
+    P.block_max = gmx_env_int("GMX_PF_BLOCK_MAX", PF_BLOCK_MAX, 0, INT64_MAX);
     if (P.block_max < P.wave_max) P.block_max = P.wave_max;
     P.cap = PF_LDS_SLOTS_MIN;   // the power of two at or below the request
-    const int64_t want = pf_env("GMX_PF_LDS_SLOTS", PF_LDS_SLOTS, PF_LDS_SLOTS_MIN, PF_LDS_SLOTS_MAX);
+    const int64_t want = gmx_env_int("GMX_PF_LDS_SLOTS", PF_LDS_SLOTS, PF_LDS_SLOTS_MIN, PF_LDS_SLOTS_MAX);
     while ((int64_t) P.cap * 2 <= want) P.cap *= 2;
     P.wcap = P.cap / PF_WAVE_SHARE;
-    P.lds_bits = pf_env("GMX_PF_LDS_BITS", PF_LDS_BITS, 1, PF_LDS_BITS_MAX);
-    P.batch_bytes = pf_env("GMX_PF_BATCH_BYTES", PF_BATCH_BYTES, 4, INT64_MAX);
+    P.lds_bits = gmx_env_int("GMX_PF_LDS_BITS", PF_LDS_BITS, 1, PF_LDS_BITS_MAX);
+    P.batch_bytes = gmx_env_int("GMX_PF_BATCH_BYTES", PF_BATCH_BYTES, 4, INT64_MAX);
     P.log = getenv("GMX_PF_LOG") != nullptr;   // a line per evaluation for tools/pf_prof.py
     const int64_t nwords = (V + 31) >> 5;
     P.lds_map = V <= P.lds_bits;

@@ -21,6 +21,7 @@
 #include <rocprim/rocprim.hpp>
 
 #define RT_THREADS 256           // = BFS_THREADS (frontier_flush copies with that stride)
+static_assert(RT_THREADS == BFS_THREADS, "frontier_flush and first_bad_slot_kernel are built for BFS_THREADS");
 #define RT_TAIL_THREADS 1024
 #define RT_TAIL 4096             // GMX_ROUTE_TAIL: the tail launch takes over while the side to expand holds at most this many slots
 #define RT_TAIL_LANE 8           // the tail reads a row of at most this many slots with one lane, a longer one with a wave
@@ -131,35 +132,6 @@ __global__ void __launch_bounds__(RT_THREADS) rt_init_kernel(rt_dev D, int32_t s
     }
 }
 
-// out->bad = E - (the first slot whose weight is negative)
-__global__ void __launch_bounds__(RT_THREADS) rt_weight_check_kernel(const int32_t* __restrict__ w, int64_t E, rt_ctl* __restrict__ out) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    rt_word worst = 0;
-    for (; i < E; i += stride)
-        if (w[i] < 0) {
-            const rt_word x = (rt_word) (E - i);
-            worst = x > worst ? x : worst;
-        }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const rt_word y = __shfl_down(worst, o, 64);
-        worst = y > worst ? y : worst;
-    }
-    if ((threadIdx.x & 63) == 0 && worst) atomicMax(&out->bad, worst);
-}
-
-// dst[j] = src[via[j]]: gather_by_order_kernel's (gmx_sssp.hip) shape, for the weights and for the slot maps
-__global__ void rt_gather_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ via, int64_t n, int32_t* __restrict__ dst) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    for (; i < n; i += stride) dst[i] = src[via[i]];
-}
-__global__ void rt_iota_kernel(int32_t* __restrict__ a, int64_t n) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    for (; i < n; i += stride) a[i] = (int32_t) i;
-}
 // the k-th reverse slot and the k-th forward slot in the order of their (dst, src) keys are the same edge
 __global__ void rt_pair_kernel(const int32_t* __restrict__ rslot, const int32_t* __restrict__ fslot, int64_t n, int32_t* __restrict__ rev2fwd) {
     int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -206,12 +178,8 @@ __global__ void __launch_bounds__(BFS_THREADS) rt_round_kernel(rt_dev D, int s, 
         degs += (rt_word) dg;
         wave_append(won, v, s_win, &s_nwin, lane);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        degs += __shfl_down(degs, o, 64);
-        const uint32_t y = __shfl_down(low, o, 64);
-        low = y < low ? y : low;
-    }
+    degs = wave_sum(degs);
+    low = wave_min(low);
     if (lane == 0) {
         if (degs) atomicAdd(&s_deg, degs);
         if (low != RT_NIL) atomicMin(&s_low, low);
@@ -234,8 +202,8 @@ struct rt_tail_args {
 };
 
 // Runs rounds until a queue is empty, L_F + L_R >= cost(mu), or the side to expand holds more than tail_from slots (the
-// grid takes over).  A queue is plain stores of this workgroup, visible to its waves behind the barrier as in
-// gmx_sssp_f64.hip.  Every round but a side's last lowers a label, and each is a bounded loop: no waiting on anybody.
+// grid takes over).  A queue is plain stores of this workgroup, visible to its waves behind the barrier; its rows are
+// walked by tail_rows (gmx_frontier.h).  Every round but a side's last lowers a label, and each is a bounded loop: no waiting on anybody.
 __global__ void __launch_bounds__(RT_TAIL_THREADS) rt_tail_kernel(rt_dev D, rt_tail_args A) {
     __shared__ unsigned int s_nnext, s_low;
     __shared__ rt_word s_mnext;
@@ -256,7 +224,7 @@ __global__ void __launch_bounds__(RT_TAIL_THREADS) rt_tail_kernel(rt_dev D, rt_t
         if (A.L[0] + (A.both ? A.L[1] : 0ull) >= muc) break;
         const int s = A.both && A.m[1] < A.m[0] ? 1 : 0;
         if (A.m[s] > A.tail_from) break;
-        const rt_side& S = D.side[s];
+        const rt_side S = D.side[s];   // (a copy: through a reference into the arguments every slot step reloaded S.label)
         const rt_side& O = D.side[1 - s];
         const rt_word L_other = A.both ? A.L[1 - s] : 0ull;
         const int32_t* la = A.q[s][0];
@@ -264,38 +232,16 @@ __global__ void __launch_bounds__(RT_TAIL_THREADS) rt_tail_kernel(rt_dev D, rt_t
         const int64_t n = A.n[s];
         rt_word degs = 0;
         uint32_t low = RT_NIL;
-        const auto slot = [&](bool on, uint32_t d, int32_t e) {   // whole wave
+        const auto slot = [&](bool on, uint32_t d, int32_t e) {
             int32_t v = 0, dg = 0;
             const bool won = rt_relax(S, O, D.ctl, on, d, e, L_other, tag, &v, &dg, &low);
             degs += (rt_word) dg;
             wave_append(won, v, lb, &s_nnext, lane);
         };
-        for (int64_t base = wave * 64; base < n; base += nwaves * 64) {   // 64 rows: a lane each, the long ones by the wave
-            const bool have = base + lane < n;
-            const int32_t v = have ? la[base + lane] : 0;
-            const int32_t b = have ? S.begin[v] : 0, e = have ? S.begin[v + 1] : 0;
-            const uint32_t d = have ? (uint32_t) (rt_load(&S.label[v]) >> 32) : 0u;
-            const bool by_wave = e - b > RT_TAIL_LANE;
-            for (int32_t k = 0; k < RT_TAIL_LANE; k++) {
-                const bool on = !by_wave && b + k < e;
-                if (!__ballot(on)) break;   // (wave-uniform)
-                slot(on, d, b + k);
-            }
-            unsigned long long lm = __ballot(by_wave);
-            while (lm) {
-                const int from = __builtin_ctzll(lm);
-                lm &= lm - 1;
-                const int32_t wb = __shfl(b, from, 64), we = __shfl(e, from, 64);
-                const uint32_t wd = __shfl(d, from, 64);
-                for (int32_t x = wb; x < we; x += 64) slot(x + lane < we, wd, x + lane);
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            degs += __shfl_down(degs, o, 64);
-            const uint32_t y = __shfl_down(low, o, 64);
-            low = y < low ? y : low;
-        }
+        const auto load = [&](bool have, int32_t v, int32_t) { return have ? (uint32_t) (rt_load(&S.label[v]) >> 32) : 0u; };
+        tail_rows<RT_TAIL_LANE>(la, n, S.begin, lane, wave, nwaves, load, slot);
+        degs = wave_sum(degs);
+        low = wave_min(low);
         if (lane == 0) {
             if (degs) atomicAdd(&s_mnext, degs);
             if (low != RT_NIL) atomicMin(&s_low, low);
@@ -421,19 +367,6 @@ struct gmx_route {
     double h2d_ms = 0;
 };
 
-static int64_t rt_env(const char* name, int64_t dflt) {
-    const char* e = getenv(name);
-    if (!e || !*e) return dflt;
-    const long long v = atoll(e);
-    return v < 0 ? 0 : (v > INT32_MAX ? INT32_MAX : v);
-}
-
-static int rt_read_ctl(gmx_route* r) {   // synchronises
-    GMX_HIP(hipMemcpyAsync(r->h_ctl.p, r->ctl.p, sizeof(rt_ctl), hipMemcpyDeviceToHost, 0));
-    GMX_HIP(hipStreamSynchronize(0));
-    return GMX_OK;
-}
-
 // rev2fwd[j] = the device forward slot that reverse slot j stands for: both CSRs' slots sorted (stably) by (dst << 32 | src)
 // pair up in order, whatever order the rows are stored in; a reverse CSR with sorted rows is in that order already
 static int rt_reverse_map(const gmx_graph* g, int32_t* rev2fwd) {
@@ -451,11 +384,11 @@ static int rt_reverse_map(const gmx_graph* g, int32_t* rev2fwd) {
     size_t tb = 0;
     GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys.p, keys2.p, val.p, fslot.p, E, 0u, end_bit, 0));
     GMX_CHECK(tmp.alloc(tb));
-    hipLaunchKernelGGL(rt_iota_kernel, dim3(grid_for(g->E)), dim3(RT_THREADS), 0, 0, val.p, g->E);
+    hipLaunchKernelGGL(iota_kernel, dim3(grid_for(g->E)), dim3(RT_THREADS), 0, 0, val.p, g->E);
     GMX_CHECK(gmx_keys_from_csr(g->begin.p, g->node_idx.p, g->V, g->E, true, nullptr, keys.p, 0));
     GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, keys.p, keys2.p, val.p, fslot.p, E, 0u, end_bit, 0));
     if (g->r_rows_sorted) {
-        hipLaunchKernelGGL(rt_iota_kernel, dim3(grid_for(g->E)), dim3(RT_THREADS), 0, 0, rslot.p, g->E);
+        hipLaunchKernelGGL(iota_kernel, dim3(grid_for(g->E)), dim3(RT_THREADS), 0, 0, rslot.p, g->E);
     } else {
         GMX_CHECK(gmx_keys_from_csr(g->r_begin.p, g->r_node_idx.p, g->V, g->E, false, nullptr, keys.p, 0));
         GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, keys.p, keys2.p, val.p, rslot.p, E, 0u, end_bit, 0));
@@ -485,16 +418,16 @@ static int rt_create(gmx_route* r, gmx_graph* g, const int32_t* weight_host) {
             up = r->w_up.p;
         }
         GMX_HIP(hipMemcpyAsync(up, weight_host, sizeof(int32_t) * E, hipMemcpyHostToDevice, 0));
-        hipLaunchKernelGGL(rt_weight_check_kernel, dim3(grid_for(g->E, RT_THREADS)), dim3(RT_THREADS), 0, 0, (const int32_t*) up, g->E, r->ctl.p);
+        hipLaunchKernelGGL((first_bad_slot_kernel<int32_t, rt_ctl>), dim3(grid_for(g->E, RT_THREADS)), dim3(RT_THREADS), 0, 0, (const int32_t*) up, g->E, r->ctl.p);
         GMX_HIP(hipGetLastError());
-        GMX_CHECK(rt_read_ctl(r));
+        GMX_CHECK(gmx_read_back(r->h_ctl, r->ctl.p));
         if (r->h_ctl.p->bad) {
             const int64_t at = g->E - (int64_t) r->h_ctl.p->bad;
             gmx_set_error("route: weight[%lld] = %d is negative: every weight must be >= 0", (long long) at, (int) weight_host[at]);
             return GMX_ERR_ARG;
         }
         if (g->e_idx2idx.p) {
-            hipLaunchKernelGGL(rt_gather_kernel, dim3(grid_for(g->E, RT_THREADS)), dim3(RT_THREADS), 0, 0, (const int32_t*) up, (const int32_t*) g->e_idx2idx.p,
+            hipLaunchKernelGGL(gather_by_order_kernel<int32_t>, dim3(grid_for(g->E, RT_THREADS)), dim3(RT_THREADS), 0, 0, (const int32_t*) up, (const int32_t*) g->e_idx2idx.p,
                                g->E, r->w_f.p);
             GMX_HIP(hipGetLastError());
             GMX_HIP(hipStreamSynchronize(0));
@@ -505,13 +438,13 @@ static int rt_create(gmx_route* r, gmx_graph* g, const int32_t* weight_host) {
             GMX_CHECK(r->w_r.alloc(E));
             GMX_CHECK(r->r2u.alloc(E));
             GMX_CHECK(rt_reverse_map(g, r->r2u.p));
-            hipLaunchKernelGGL(rt_gather_kernel, dim3(grid_for(g->E, RT_THREADS)), dim3(RT_THREADS), 0, 0, (const int32_t*) r->w_f.p, (const int32_t*) r->r2u.p,
+            hipLaunchKernelGGL(gather_by_order_kernel<int32_t>, dim3(grid_for(g->E, RT_THREADS)), dim3(RT_THREADS), 0, 0, (const int32_t*) r->w_f.p, (const int32_t*) r->r2u.p,
                                g->E, r->w_r.p);
             if (g->e_idx2idx.p) {
                 dbuf<int32_t> dev_slot;
                 GMX_CHECK(dev_slot.alloc(E));
                 GMX_HIP(hipMemcpyAsync(dev_slot.p, r->r2u.p, sizeof(int32_t) * E, hipMemcpyDeviceToDevice, 0));
-                hipLaunchKernelGGL(rt_gather_kernel, dim3(grid_for(g->E, RT_THREADS)), dim3(RT_THREADS), 0, 0, (const int32_t*) g->e_idx2idx.p,
+                hipLaunchKernelGGL(gather_by_order_kernel<int32_t>, dim3(grid_for(g->E, RT_THREADS)), dim3(RT_THREADS), 0, 0, (const int32_t*) g->e_idx2idx.p,
                                    (const int32_t*) dev_slot.p, g->E, r->r2u.p);
                 GMX_HIP(hipGetLastError());
                 GMX_HIP(hipStreamSynchronize(0));
@@ -565,8 +498,8 @@ extern "C" int gmx_route_query(gmx_route_t* r, gmx_node_t src, gmx_node_t dst, i
     GMX_REQUIRE(src >= 0 && src < V, "route: src = %d is not a vertex of [0, %lld)", (int) src, (long long) V);
     GMX_REQUIRE(dst >= 0 && dst < V, "route: dst = %d is not a vertex of [0, %lld)", (int) dst, (long long) V);
     if (stats) memset(stats, 0, sizeof(*stats));
-    const int64_t tail_from = rt_env("GMX_ROUTE_TAIL", RT_TAIL);   // the knobs are read at every call; flag and cost do not depend on them
-    const int64_t log = rt_env("GMX_ROUTE_LOG", 0);
+    const int64_t tail_from = gmx_env_int("GMX_ROUTE_TAIL", RT_TAIL, 0, INT32_MAX);   // the knobs are read at every call; flag and cost do not depend on them
+    const int64_t log = gmx_env_int("GMX_ROUTE_LOG", 0, 0, INT32_MAX);
     const char* sides = getenv("GMX_ROUTE_SIDES");
     const bool both = r->has_reverse && !(sides && !strcmp(sides, "forward"));
     const double t_start = gmx_tick::now();
@@ -594,7 +527,7 @@ extern "C" int gmx_route_query(gmx_route_t* r, gmx_node_t src, gmx_node_t dst, i
     GMX_HIP(hipEventRecord(ev[0], 0));
     hipLaunchKernelGGL(rt_init_kernel, dim3(grid_for(V, RT_THREADS)), dim3(RT_THREADS), 0, 0, D, (int32_t) src, (int32_t) dst, r->pos.p, r->q[0][0].p, r->q[1][0].p);
     GMX_HIP(hipGetLastError());
-    GMX_CHECK(rt_read_ctl(r));
+    GMX_CHECK(gmx_read_back(r->h_ctl, r->ctl.p));
     int32_t* q[2][2] = {{r->q[0][0].p, r->q[0][1].p}, {r->q[1][0].p, r->q[1][1].p}};   // [side][0]: the side's queue
     int64_t m[2] = {(int64_t) h->seed_deg[0], (int64_t) h->seed_deg[1]};
     int64_t n[2] = {m[0] > 0 ? 1 : 0, m[1] > 0 ? 1 : 0};
@@ -620,7 +553,7 @@ extern "C" int gmx_route_query(gmx_route_t* r, gmx_node_t src, gmx_node_t dst, i
             A.both = both ? 1 : 0;
             hipLaunchKernelGGL(rt_tail_kernel, dim3(1), dim3(RT_TAIL_THREADS), 0, 0, D, A);
             GMX_HIP(hipGetLastError());
-            GMX_CHECK(rt_read_ctl(r));
+            GMX_CHECK(gmx_read_back(r->h_ctl, r->ctl.p));
             tail_launches++;
             for (int x = 0; x < 2; x++) {
                 const int32_t ran = (int32_t) h->tail_rounds[x];
@@ -641,7 +574,7 @@ extern "C" int gmx_route_query(gmx_route_t* r, gmx_node_t src, gmx_node_t dst, i
             hipLaunchKernelGGL(rt_round_kernel, dim3((unsigned) nb), dim3(BFS_THREADS), 0, 0, D, s, (const int32_t*) q[s][0], n[s],
                                (const int64_t*) r->fs.off.p, m[s], both ? L[1 - s] : 0ull, tag, q[s][1]);
             GMX_HIP(hipGetLastError());
-            GMX_CHECK(rt_read_ctl(r));
+            GMX_CHECK(gmx_read_back(r->h_ctl, r->ctl.p));
             grid_rounds[s]++;
             slots[s] += m[s];
             tag++;
@@ -659,7 +592,7 @@ extern "C" int gmx_route_query(gmx_route_t* r, gmx_node_t src, gmx_node_t dst, i
         hipLaunchKernelGGL(rt_extract_kernel, dim3(1), dim3(64), 0, 0, D, (const int32_t*) g->e_idx2idx.p, (const int32_t*) r->r2u.p, r->pos.p, q[1][0], q[1][1],
                            q[0][0], q[0][1], r->out_n.p, r->out_e.p);
         GMX_HIP(hipGetLastError());
-        GMX_CHECK(rt_read_ctl(r));
+        GMX_CHECK(gmx_read_back(r->h_ctl, r->ctl.p));
         GMX_REQUIRE(h->bad == 0, "route: a predecessor chain did not end");
         nhops = (int64_t) h->hops;
     }

@@ -41,8 +41,7 @@ sssp_relax_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__
         if (nd < dist[s] && nd < atomicMin(&dist[s], nd)) won = atomicExch(&stamp[s], round) != round;
         wave_append(won, s, s_win, &s_nwin, tid & 63);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) inspected += __shfl_down(inspected, o, 64);
+    inspected = wave_sum(inspected);
     if ((tid & 63) == 0) bfs_count(ctr, inspected, 0);
     __syncthreads();
     const unsigned int nwin = s_nwin;
@@ -57,13 +56,6 @@ __global__ void sssp_init_kernel(int32_t* __restrict__ dist, int32_t* __restrict
         dist[i] = (i == root) ? 0 : INT_MAX;
         stamp[i] = -1;
     }
-}
-
-// dst[j] = src[order[j]]: an edge property given by uploaded slot, brought into the order of the sorted rows
-__global__ void gather_by_order_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ order, int64_t n, int32_t* __restrict__ dst) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    for (; i < n; i += stride) dst[i] = src[order[i]];
 }
 
 // What the two relaxation entries share: the round queues and their stamp, the queue's merge-path offsets, the counters with
@@ -95,7 +87,7 @@ struct relax_scratch {
     int reorder_len(const gmx_graph* g) {
         if (!g->E || !g->e_idx2idx.p) return GMX_OK;
         GMX_CHECK(len_sorted.alloc((size_t) g->E));
-        hipLaunchKernelGGL(gather_by_order_kernel, dim3(grid_for(g->E)), dim3(BFS_THREADS), 0, 0, (const int32_t*) len.p,
+        hipLaunchKernelGGL(gather_by_order_kernel<int32_t>, dim3(grid_for(g->E)), dim3(BFS_THREADS), 0, 0, (const int32_t*) len.p,
                            (const int32_t*) g->e_idx2idx.p, g->E, len_sorted.p);
         len_dev = len_sorted.p;
         return GMX_OK;
@@ -104,11 +96,6 @@ struct relax_scratch {
     int offsets(const gmx_graph* g, const int32_t* q, int64_t n, int64_t* m_f) {
         GMX_CHECK(gmx_frontier_offsets(g->begin.p, q, n, &fs, h_mf.p, true));
         *m_f = *h_mf.p;
-        return GMX_OK;
-    }
-    int read_counters() {   // synchronises
-        GMX_HIP(hipMemcpyAsync(h_ctr.p, ctr.p, sizeof(bfs_counters), hipMemcpyDeviceToHost, 0));
-        GMX_HIP(hipStreamSynchronize(0));
         return GMX_OK;
     }
 };
@@ -152,7 +139,7 @@ extern "C" int gmx_sssp(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host
             hipLaunchKernelGGL(sssp_relax_kernel, dim3((unsigned) nb), dim3(BFS_THREADS), 0, 0, g->begin.p, g->node_idx.p,
                                S.len_dev, cur_q, cur_count, S.fs.off.p, m_f, round, dist.p, S.stamp.p, next_q, ctr, (const int64_t*) S.fs.split.p);
         GMX_HIP(hipGetLastError());
-        GMX_CHECK(S.read_counters());
+        GMX_CHECK(gmx_read_back(S.h_ctr, S.ctr.p));
         const bfs_counters& h = *S.h_ctr.p;
         unsigned long long found_unused = 0;
         cur_count = (int64_t) h.next_count;
@@ -227,11 +214,8 @@ sp_len_check_kernel(const int32_t* __restrict__ len, int64_t E, unsigned long lo
         neg += l < 0;
         sum += l < 0 ? 0ull : (unsigned long long) l;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        neg += __shfl_down(neg, o, 64);
-        sum += __shfl_down(sum, o, 64);
-    }
+    neg = wave_sum(neg);
+    sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0) {
         s_neg[threadIdx.x >> 6] = neg;
         s_sum[threadIdx.x >> 6] = sum;
@@ -303,8 +287,7 @@ sp_relax_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ n
         wave_append(to_queue, s, s_win, &s_nwin, lane);
         if (NEARFAR) wave_append(to_pile, s, s_far, &s_nfar, lane);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) inspected += __shfl_down(inspected, o, 64);
+    inspected = wave_sum(inspected);
     if (lane == 0) bfs_count(ctr, inspected, 0);
     __syncthreads();
     const unsigned int nwin = s_nwin, nfar = NEARFAR ? s_nfar : 0u;
@@ -361,11 +344,7 @@ sp_refilter_kernel(const int32_t* __restrict__ far_in, int64_t n, const unsigned
         wave_append(to_queue, v, s_win, &s_nwin, lane);
         wave_append(to_pile, v, s_far, &s_nfar, lane);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_down(nearest, o, 64);
-        nearest = t > nearest ? t : nearest;
-    }
+    nearest = wave_max(nearest);
     if (lane == 0 && nearest) atomicMax(&s_nearest, nearest);
     __syncthreads();
     const unsigned int nwin = s_nwin, nfar = s_nfar;
@@ -391,12 +370,7 @@ __global__ void sp_finish_kernel(const unsigned long long* __restrict__ key, con
         dist[v] = (int32_t) (k >> 32);
         int32_t pn = -1, pe = -1;
         if (e != SP_NIL) {
-            int64_t lo = 0, hi = V - 1;   // the last row that starts at or before e (the empty rows before it start there too)
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if ((uint32_t) begin[mid] <= e) lo = mid; else hi = mid - 1;
-            }
-            pn = (int32_t) lo;
+            pn = csr_row_of(begin, V, e);
             pe = e_idx2idx ? e_idx2idx[e] : (int32_t) e;
         }
         prev_node[v] = pn;
@@ -482,7 +456,7 @@ extern "C" int gmx_sssp_path(gmx_graph_t* g, gmx_node_t root, const int32_t* len
         hipLaunchKernelGGL(sp_refilter_kernel, dim3((unsigned) ((far_n + BFS_ITEMS - 1) / BFS_ITEMS)), dim3(BFS_THREADS), 0, 0,
                            (const int32_t*) far_cur, far_n, (const unsigned long long*) key.p, S.stamp.p, tag, t_old, t_new, cur_q, far_alt, ctr);
         GMX_HIP(hipGetLastError());
-        GMX_CHECK(S.read_counters());
+        GMX_CHECK(gmx_read_back(S.h_ctr, S.ctr.p));
         tag++;
         *near_n = (int64_t) h_ctr->next_count;
         far_n = (int64_t) h_ctr->pad0[SP_FAR_TAIL];
@@ -515,7 +489,7 @@ extern "C" int gmx_sssp_path(gmx_graph_t* g, gmx_node_t root, const int32_t* len
                                        (const int64_t*) S.fs.split.p);
             }
             GMX_HIP(hipGetLastError());
-            GMX_CHECK(S.read_counters());
+            GMX_CHECK(gmx_read_back(S.h_ctr, S.ctr.p));
             const bfs_counters& h = *h_ctr;
             unsigned long long found_unused = 0;
             cur_count = (int64_t) h.next_count;

@@ -29,6 +29,7 @@
 #include <float.h>
 
 #define SPF_THREADS 256          // = BFS_THREADS (frontier_flush copies with that stride)
+static_assert(SPF_THREADS == BFS_THREADS, "frontier_flush and first_bad_slot_kernel are built for BFS_THREADS");
 #define SPF_CHUNK 2048           // list entries a workgroup of the commit kernel compacts in LDS
 #define SPF_TAIL_THREADS 1024
 #define SPF_TAIL 4096            // GMX_SSSP_F64_TAIL: the tail launch takes over while the queued rows hold at most this many slots
@@ -71,11 +72,6 @@ __device__ __forceinline__ void spf_store(spf_word* p, spf_word v) { __hip_atomi
 __device__ __forceinline__ double spf_dist(const spf_state& S, int32_t v) { return __longlong_as_double((long long) spf_load(&S.dist[v])); }
 // end.dist as the round finds it
 __device__ __forceinline__ double spf_bound(const spf_state& S) { return S.end >= 0 ? spf_dist(S, S.end) : DBL_MAX; }
-__device__ __forceinline__ spf_word spf_wave_sum(spf_word x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;   // (lane 0)
-}
 
 // ------------------------------------------------------------------ round pieces (shared by the grid kernels and the tail)
 // slot e = n -> s of a queued n at distance d: s.dist_nxt min= d + cost[e], below the bound B only
@@ -104,16 +100,6 @@ __device__ __forceinline__ bool spf_winner(const spf_state& S, bool on, double d
     return false;
 }
 
-// the row that holds uploaded slot e: the last one that starts at or before it (the empty rows before it start there too)
-__device__ __forceinline__ int32_t spf_row_of(const int32_t* __restrict__ begin, int64_t V, uint32_t e) {
-    int64_t lo = 0, hi = V - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if ((uint32_t) begin[mid] <= e) lo = mid; else hi = mid - 1;
-    }
-    return (int32_t) lo;
-}
-
 // v dropped in the round: commit it.  Returns the slots of its row when the next round walks it (bn: the bit pattern of the
 // next round's bound), else 0.
 __device__ __forceinline__ int32_t spf_commit(const spf_state& S, int32_t v, spf_word bn) {
@@ -121,7 +107,7 @@ __device__ __forceinline__ int32_t spf_commit(const spf_state& S, int32_t v, spf
     spf_store(&S.dist[v], nd);
     const uint32_t slot = ~(uint32_t) spf_load(&S.win[v]);
     S.prev_edge[v] = (int32_t) slot;
-    S.prev_node[v] = spf_row_of(S.begin, S.V, slot);
+    S.prev_node[v] = csr_row_of(S.begin, S.V, slot);
     return nd < bn ? S.begin[v + 1] - S.begin[v] : 0;
 }
 __device__ __forceinline__ spf_word spf_next_bound(const spf_state& S) { return S.end >= 0 ? spf_load(&S.dnxt[S.end]) : SPF_MAX_BITS; }
@@ -146,31 +132,6 @@ __global__ void __launch_bounds__(SPF_THREADS) spf_init_kernel(spf_state S, int3
         S.prev_node[i] = -1;
         S.prev_edge[i] = -1;
     }
-}
-
-// out->bad = E - (the first slot with !(cost >= 0): negative or NaN; -0.0 passes)
-__global__ void __launch_bounds__(SPF_THREADS) spf_cost_check_kernel(const double* __restrict__ cost, int64_t E, spf_counters* __restrict__ out) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    spf_word worst = 0;
-    for (; i < E; i += stride)
-        if (!(cost[i] >= 0.0)) {
-            const spf_word w = (spf_word) (E - i);
-            worst = w > worst ? w : worst;
-        }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const spf_word y = __shfl_down(worst, o, 64);
-        worst = y > worst ? y : worst;
-    }
-    if ((threadIdx.x & 63) == 0 && worst) atomicMax(&out->bad, worst);
-}
-
-// dst[j] = src[order[j]] for 8-byte values: gather_by_order_kernel's (gmx_sssp.hip) sibling
-__global__ void spf_gather_by_order_kernel(const double* __restrict__ src, const int32_t* __restrict__ order, int64_t n, double* __restrict__ dst) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    for (; i < n; i += stride) dst[i] = src[order[i]];
 }
 
 // the rows of the queue q[0 .. n), m slots in all, cut into merge-path tiles: the offers of round r, or (WINNER) their winners
@@ -238,7 +199,7 @@ __global__ void __launch_bounds__(SPF_THREADS) spf_commit_kernel(spf_state S, in
         deg += (spf_word) dg;
         wave_append(dg > 0, v, s_win, &s_nwin, lane);
     }
-    deg = spf_wave_sum(deg);
+    deg = wave_sum(deg);
     if (lane == 0 && deg) atomicAdd(&s_deg, deg);
     __syncthreads();
     frontier_flush(s_win, s_nwin, &S.ctr->nnext, next, &s_base, [&] {
@@ -249,8 +210,8 @@ __global__ void __launch_bounds__(SPF_THREADS) spf_commit_kernel(spf_state S, in
 // ------------------------------------------------------------------ the tail: one workgroup runs rounds in one launch
 // la[0 .. n): the queue of round r, m slots in its rows.  Runs rounds until nothing dropped, the queue is empty, or its rows
 // hold more than tail_from slots (the grid takes over again); leaves the last round's counts, the queue in la or lb by the
-// parity of the rounds run.  The lists are plain stores of this workgroup, visible to its waves behind the barrier as in
-// gmx_match.hip.  Every round but the last lowers a distance, each a bounded loop: no waiting on anybody.
+// parity of the rounds run.  The lists are plain stores of this workgroup, visible to its waves behind the barrier.  The
+// rows are walked by tail_rows (gmx_frontier.h).  Every round but the last lowers a distance, each a bounded loop: no waiting on anybody.
 __global__ void __launch_bounds__(SPF_TAIL_THREADS) spf_tail_kernel(spf_state S, int32_t* la, int32_t* lb, int64_t n, int64_t m, int32_t r,
                                                                     int64_t tail_from) {
     __shared__ unsigned int s_ntouch, s_nnext;
@@ -269,7 +230,7 @@ __global__ void __launch_bounds__(SPF_TAIL_THREADS) spf_tail_kernel(spf_state S,
     for (;;) {
         const double B = spf_bound(S);
         for (int pass = 0; pass < 2; pass++) {   // the offers, a barrier, their winners
-            const auto slot = [&](bool on, double d, int32_t e) {   // whole wave
+            const auto slot = [&](bool on, double d, int32_t e) {
                 if (pass == 0) {
                     spf_offer(S, on, d, e, B);
                 } else {
@@ -278,26 +239,8 @@ __global__ void __launch_bounds__(SPF_TAIL_THREADS) spf_tail_kernel(spf_state S,
                     wave_append(touch, s, S.touched, &s_ntouch, lane);
                 }
             };
-            for (int64_t base = wave * 64; base < n; base += nwaves * 64) {   // 64 rows: a lane each, the long ones by the wave
-                const bool have = base + lane < n;
-                const int32_t v = have ? la[base + lane] : 0;
-                const int32_t b = have ? S.begin[v] : 0, e = have ? S.begin[v + 1] : 0;
-                const double d = have ? spf_dist(S, v) : 0.0;
-                const bool by_wave = e - b > SPF_TAIL_LANE;
-                for (int32_t k = 0; k < SPF_TAIL_LANE; k++) {
-                    const bool on = !by_wave && b + k < e;
-                    if (!__ballot(on)) break;   // (wave-uniform)
-                    slot(on, d, b + k);
-                }
-                unsigned long long lm = __ballot(by_wave);
-                while (lm) {
-                    const int src = __builtin_ctzll(lm);
-                    lm &= lm - 1;
-                    const int32_t wb = __shfl(b, src, 64), we = __shfl(e, src, 64);
-                    const double wd = __shfl(d, src, 64);
-                    for (int32_t x = wb; x < we; x += 64) slot(x + lane < we, wd, x + lane);
-                }
-            }
+            const auto load = [&](bool have, int32_t v, int32_t) { return have ? spf_dist(S, v) : 0.0; };
+            tail_rows<SPF_TAIL_LANE>(la, n, S.begin, lane, wave, nwaves, load, slot);
             __syncthreads();
         }
         nt = (int64_t) s_ntouch;
@@ -313,7 +256,7 @@ __global__ void __launch_bounds__(SPF_TAIL_THREADS) spf_tail_kernel(spf_state S,
             deg += (spf_word) dg;
             wave_append(dg > 0, v, lb, &s_nnext, lane);
         }
-        deg = spf_wave_sum(deg);
+        deg = wave_sum(deg);
         if (lane == 0 && deg) atomicAdd(&s_mnext, deg);
         __syncthreads();
         slots += (spf_word) m;
@@ -371,13 +314,6 @@ struct spf_scratch {
 };
 void gmx_spf_scratch_free(spf_scratch* s) { delete s; }
 
-static int64_t spf_env(const char* name, int64_t dflt) {
-    const char* e = getenv(name);
-    if (!e || !*e) return dflt;
-    const long long v = atoll(e);
-    return v < 0 ? 0 : (v > INT32_MAX ? INT32_MAX : v);
-}
-
 extern "C" int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end, const double* cost_host, double* dist_host,
                                  gmx_node_t* prev_node_host, gmx_edge_t* prev_edge_host, gmx_stats_t* stats) {
     GMX_REQUIRE(g && dist_host && prev_node_host, "NULL argument");
@@ -387,8 +323,8 @@ extern "C" int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end
     GMX_REQUIRE(cost_host || E == 0, "sssp_path_f64: cost is NULL");
     GMX_REQUIRE(end == -1 || (end >= 0 && end < V), "sssp_path_f64: end = %d is neither -1 (no target) nor a vertex of [0, %lld)", (int) end, (long long) V);
     const bool root_ok = root >= 0 && root < V;
-    const int64_t tail_from = spf_env("GMX_SSSP_F64_TAIL", SPF_TAIL);   // read at every call; the result does not depend on it
-    const int64_t log = spf_env("GMX_SSSP_F64_LOG", 0);                 // 1: one line per call; 2: a line per grid round and tail launch before it
+    const int64_t tail_from = gmx_env_int("GMX_SSSP_F64_TAIL", SPF_TAIL, 0, INT32_MAX);   // read at every call; the result does not depend on it
+    const int64_t log = gmx_env_int("GMX_SSSP_F64_LOG", 0, 0, INT32_MAX);                 // 1: one line per call; 2: a line per grid round and tail launch before it
 
     if (!g->spf_cache) {
         spf_scratch* fresh = new spf_scratch;
@@ -418,27 +354,22 @@ extern "C" int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end
     S.V = V;
     S.end = end;
     spf_counters* h = W.h_ctr.p;
-    auto read_ctr = [&]() -> int {   // synchronises
-        GMX_HIP(hipMemcpyAsync(h, W.ctr.p, sizeof(spf_counters), hipMemcpyDeviceToHost, 0));
-        GMX_HIP(hipStreamSynchronize(0));
-        return GMX_OK;
-    };
 
     // the property: copied in, checked on the device copy, brought into the order of the sorted rows when the upload sorted them
     GMX_HIP(hipEventRecord(ev[0], 0));
     GMX_HIP(hipMemsetAsync(W.ctr.p, 0, sizeof(spf_counters), 0));
     if (E) {
         GMX_HIP(hipMemcpyAsync(W.cost.p, cost_host, sizeof(double) * (size_t) E, hipMemcpyHostToDevice, 0));
-        hipLaunchKernelGGL(spf_cost_check_kernel, dim3(grid_for(E, SPF_THREADS)), dim3(SPF_THREADS), 0, 0, (const double*) W.cost.p, E, W.ctr.p);
+        hipLaunchKernelGGL((first_bad_slot_kernel<double, spf_counters>), dim3(grid_for(E, SPF_THREADS)), dim3(SPF_THREADS), 0, 0, (const double*) W.cost.p, E, W.ctr.p);
         GMX_HIP(hipGetLastError());
-        GMX_CHECK(read_ctr());
+        GMX_CHECK(gmx_read_back(W.h_ctr, W.ctr.p));
         if (h->bad) {
             const int64_t at = E - (int64_t) h->bad;
             gmx_set_error("sssp_path_f64: cost[%lld] = %g is negative or not a number: every cost must be >= 0", (long long) at, cost_host[at]);
             return GMX_ERR_ARG;
         }
         if (g->e_idx2idx.p) {
-            hipLaunchKernelGGL(spf_gather_by_order_kernel, dim3(grid_for(E, SPF_THREADS)), dim3(SPF_THREADS), 0, 0, (const double*) W.cost.p,
+            hipLaunchKernelGGL(gather_by_order_kernel<double>, dim3(grid_for(E, SPF_THREADS)), dim3(SPF_THREADS), 0, 0, (const double*) W.cost.p,
                                (const int32_t*) g->e_idx2idx.p, E, W.cost_sorted.p);
             S.cost = W.cost_sorted.p;
         }
@@ -451,7 +382,7 @@ extern "C" int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end
     int32_t* lb = W.q1.p;
     hipLaunchKernelGGL(spf_init_kernel, dim3(grid_for(V, SPF_THREADS)), dim3(SPF_THREADS), 0, 0, S, root_ok ? root : -1, la);
     GMX_HIP(hipGetLastError());
-    GMX_CHECK(read_ctr());
+    GMX_CHECK(gmx_read_back(W.h_ctr, W.ctr.p));
     int64_t n = (int64_t) h->nnext, m = (int64_t) h->mnext;
     int64_t queued = (int64_t) h->ntouch, grid_slots = 0, tail_slots = 0;
     int32_t rounds = 0, grid_rounds = 0, tail_rounds = 0, tail_launches = 0;
@@ -462,7 +393,7 @@ extern "C" int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end
         if (tail_from > 0 && m <= tail_from) {   // one workgroup, until the queue outgrows it
             hipLaunchKernelGGL(spf_tail_kernel, dim3(1), dim3(SPF_TAIL_THREADS), 0, 0, S, la, lb, n, m, rounds + 1, tail_from);
             GMX_HIP(hipGetLastError());
-            GMX_CHECK(read_ctr());
+            GMX_CHECK(gmx_read_back(W.h_ctr, W.ctr.p));
             const int32_t ran = (int32_t) h->tail_rounds;
             rounds += ran;
             tail_rounds += ran;
@@ -483,7 +414,7 @@ extern "C" int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end
             const int64_t most = m < V ? m : V;   // a slot drops at most one vertex
             hipLaunchKernelGGL(spf_commit_kernel, dim3((unsigned) ((most + SPF_CHUNK - 1) / SPF_CHUNK)), dim3(SPF_THREADS), 0, 0, S, lb);
             GMX_HIP(hipGetLastError());
-            GMX_CHECK(read_ctr());
+            GMX_CHECK(gmx_read_back(W.h_ctr, W.ctr.p));
             rounds++;
             grid_rounds++;
             grid_slots += m;

@@ -390,13 +390,6 @@ static int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
     return GMX_OK;
 }
 
-static int tcd_env(const char* name, int dflt, int lo, int hi) {
-    const char* e = getenv(name);
-    if (!e || !*e) return dflt;
-    const long long v = atoll(e);
-    return (int) (v < lo ? lo : (v > hi ? hi : v));
-}
-
 static int tcd_count_part(gmx_graph_t* g, int part, int nparts, int64_t* count, gmx_stats_t* stats) {
     GMX_REQUIRE(g && count, "NULL argument");
     GMX_REQUIRE(nparts >= 1 && part >= 0 && part < nparts, "bad part %d / nparts %d", part, nparts);
@@ -405,9 +398,9 @@ static int tcd_count_part(gmx_graph_t* g, int part, int nparts, int64_t* count, 
     if (g->V == 0 || g->E == 0) return GMX_OK;
     // knobs, read at every call; the count does not depend on them
     const bool ordered = !getenv("GMX_TCD_NO_ORDER");
-    const int cap = tcd_env("GMX_TCD_CAP", TCD_CAP, TCD_CAP_MIN, TCD_CAP);
-    const int alone = tcd_env("GMX_TCD_ALONE", TCD_ALONE, 0, INT32_MAX);
-    const int ratio = tcd_env("GMX_TCD_RATIO", TCD_RATIO, 0, INT32_MAX);
+    const int cap = (int) gmx_env_int("GMX_TCD_CAP", TCD_CAP, TCD_CAP_MIN, TCD_CAP);
+    const int alone = (int) gmx_env_int("GMX_TCD_ALONE", TCD_ALONE, 0, INT32_MAX);
+    const int ratio = (int) gmx_env_int("GMX_TCD_RATIO", TCD_RATIO, 0, INT32_MAX);
     // graph preprocessing (cached on the graph like the reverse CSR; outside the timed region)
     bool built = false;
     if (g->tcd_cache && g->tcd_cache->ordered != ordered) {

@@ -106,11 +106,7 @@ __global__ void vc_low_kernel(const int32_t* __restrict__ off, const int2* __res
             const unsigned long long w = ((unsigned long long) (uint32_t) ent[i].y << 32) | (uint32_t) i;
             m = w < m ? w : m;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long w = __shfl_down(m, o, 64);
-            m = w < m ? w : m;
-        }
+        m = wave_min(m);
         if (lane == 0) low[v] = b < e ? (int32_t) (uint32_t) m : -1;
     }
 }
@@ -221,8 +217,7 @@ __device__ __forceinline__ void vc_pick(const vc_state& S, const int32_t* act, i
     }
     wave_append(rec, u, newq, &S.ctr[VC_NCOV], lane);
     wave_append(addx, x, newq, &S.ctr[VC_NCOV], lane);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) len += __shfl_down(len, o, 64);
+    len = wave_sum(len);
     if (lane == 0) atomicAdd(&S.ctr[VC_MCOV], len);
     if (__ballot(self) && lane == leader) S.ctr[VC_SELF] = 1;
 }
@@ -237,8 +232,7 @@ __device__ __forceinline__ bool vc_wakes(const vc_state& S, int2 en, int32_t r) 
 }
 
 __device__ __forceinline__ void vc_count(const vc_state& S, int which, unsigned long long n, int lane) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o, 64);
+    n = wave_sum(n);
     if (lane == 0 && n) atomicAdd(&S.ctr[which], n);
 }
 
@@ -446,13 +440,6 @@ static int vc_build_plan(const gmx_graph* g, vc_plan** out) {
     return GMX_OK;
 }
 
-static int64_t vc_env(const char* name, int64_t dflt) {
-    const char* e = getenv(name);
-    if (!e || !*e) return dflt;
-    const long long v = atoll(e);
-    return v < 0 ? 0 : (v > INT32_MAX ? INT32_MAX : v);
-}
-
 extern "C" int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host, int32_t* covered, gmx_stats_t* stats) {
     GMX_REQUIRE(g && covered, "NULL argument");
     GMX_REQUIRE(select_host || g->E == 0, "select is NULL");
@@ -466,8 +453,8 @@ extern "C" int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host, int32_t* covere
     }
     GMX_REQUIRE(E < (1LL << 30), "v_cover: %lld edges: the incident lists keep 32-bit offsets (below 2^30 edges)", (long long) E);
     // knobs, read at every call; the result does not depend on them
-    const int64_t tail_from = vc_env("GMX_VC_TAIL", VC_TAIL);
-    const int64_t wave_min = vc_env("GMX_VC_WAVE", VC_WAVE);
+    const int64_t tail_from = gmx_env_int("GMX_VC_TAIL", VC_TAIL, 0, INT32_MAX);
+    const int64_t wave_min = gmx_env_int("GMX_VC_WAVE", VC_WAVE, 0, INT32_MAX);
     bool built = false;
     if (!g->vc_cache) {
         GMX_CHECK(vc_build_plan(g, &g->vc_cache));
@@ -515,11 +502,6 @@ extern "C" int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host, int32_t* covere
     S.V = V;
     S.wave_min = (int32_t) wave_min;
     unsigned long long* h = h_ctr.p;
-    auto read_ctr = [&]() -> int {   // synchronises
-        GMX_HIP(hipMemcpyAsync(h, ctr.p, VC_NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost, 0));
-        GMX_HIP(hipStreamSynchronize(0));
-        return GMX_OK;
-    };
 
     GMX_HIP(hipEventRecord(ev[0], 0));
     const double t_start = gmx_tick::now();
@@ -541,7 +523,7 @@ extern "C" int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host, int32_t* covere
             hipLaunchKernelGGL(vc_tail_kernel, dim3(1), dim3(VC_TAIL_THREADS), 0, 0, S, act.p, qa, qb, ncov, first ? 1 : 0, round + 1, tail_out.p);
             GMX_HIP(hipGetLastError());
             GMX_HIP(hipMemcpy(&tail_rounds, tail_out.p, sizeof(int32_t), hipMemcpyDeviceToHost));
-            GMX_CHECK(read_ctr());
+            GMX_CHECK(gmx_read_back(h_ctr, ctr.p, VC_NCTR));
             tail_ms = (gmx_tick::now() - t_tail0) * 1e3;
             break;
         }
@@ -561,7 +543,7 @@ extern "C" int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host, int32_t* covere
         hipLaunchKernelGGL(vc_eval_kernel, dim3(vc_grid(bound)), dim3(VC_THREADS), 0, 0, S, a, nptr, V);
         hipLaunchKernelGGL(vc_pick_kernel, dim3(vc_grid(bound)), dim3(VC_THREADS), 0, 0, S, a, nptr, V, round + 1, qb);
         GMX_HIP(hipGetLastError());
-        GMX_CHECK(read_ctr());
+        GMX_CHECK(gmx_read_back(h_ctr, ctr.p, VC_NCTR));
         last_active = (int64_t) (h[VC_ACTSUM] - actsum);
         actsum = h[VC_ACTSUM];
         if (last_active == 0) break;   // nothing woke up: the round did not take place
@@ -600,7 +582,7 @@ extern "C" int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host, int32_t* covere
         hipLaunchKernelGGL(vc_kept_kernel, dim3(vc_grid(picks)), dim3(VC_THREADS), 0, 0, (const unsigned long long*) pre.p, picks,
                            2ULL * (unsigned long long) E, S);
         GMX_HIP(hipGetLastError());
-        GMX_CHECK(read_ctr());
+        GMX_CHECK(gmx_read_back(h_ctr, ctr.p, VC_NCTR));
         kept = (int64_t) h[VC_KEPT];   // (the sums never fall: the kept picks are the first `kept` of the order; at least one)
         GMX_HIP(hipMemcpy(&least, sorted + (kept - 1), sizeof(least), hipMemcpyDeviceToHost));
     }
@@ -608,7 +590,7 @@ extern "C" int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host, int32_t* covere
         hipLaunchKernelGGL(vc_select_kernel, dim3(vc_grid(picks)), dim3(VC_THREADS), 0, 0, S, picks, least, select.p);
         GMX_HIP(hipGetLastError());
     }
-    GMX_CHECK(read_ctr());
+    GMX_CHECK(gmx_read_back(h_ctr, ctr.p, VC_NCTR));
     GMX_HIP(hipEventRecord(ev[1], 0));
     const double t_finish = gmx_tick::now();
     GMX_HIP(hipEventRecord(ev[2], 0));
