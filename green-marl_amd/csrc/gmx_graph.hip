@@ -396,6 +396,7 @@ void gmx_warm_modules() {
     gmx_touch_match();
     gmx_touch_spf();
     gmx_touch_route();
+    gmx_touch_walk();
 }
 
 static int check_sizes(int64_t V, int64_t E) {

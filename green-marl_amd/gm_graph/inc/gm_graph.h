@@ -51,6 +51,10 @@ class gm_graph
 
     node_t num_nodes() { return _numNodes; }
     node_t pick_random_node() { return rand() % num_nodes(); }   // G.PickRandom(): one libc rand() draw (gm_graph.h:389-391)
+    // n.PickRandomNbr(): one draw of the calling thread's gm_rt_uniform stream, slot (edge_t) (u * (double) deg) of the row as
+    // stored; the row must not be empty.  (The reference's returns node_idx[begin[node]] + rand() % outCount -- the offset
+    // added to a vertex id, gm_graph.h:379-391 -- and is not reproduced.)
+    node_t pick_random_out_neighbor(node_t node);
     edge_t num_edges() { return _numEdges; }
     bool has_reverse_edge() { return _reverse_edge; }
     bool is_frozen() { return _frozen; }

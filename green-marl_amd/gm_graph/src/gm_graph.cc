@@ -10,6 +10,7 @@
 
 #include <omp.h>
 
+#include "gm_runtime.h"
 #include "gmx.h"
 
 // edge offsets cross the C ABI as edge_t: a GM_EDGE64 build of this library uses the 64-bit variants of the graph calls
@@ -241,6 +242,12 @@ edge_t gm_graph::get_edge_idx_for_src_dest(node_t src, node_t to) {
     const node_t* hi = node_idx + begin[src + 1];
     const node_t* p = std::lower_bound(lo, hi, to);
     return (p != hi && *p == to) ? (edge_t) (p - node_idx) : NIL_EDGE;
+}
+
+node_t gm_graph::pick_random_out_neighbor(node_t node) {
+    const edge_t deg = begin[node + 1] - begin[node];
+    assert(deg > 0);
+    return node_idx[begin[node] + (edge_t) (gm_rt_uniform(gm_rt_thread_id()) * (double) deg)];
 }
 
 bool gm_graph::is_neighbor(node_t src, node_t to) { return get_edge_idx_for_src_dest(src, to) != NIL_EDGE; }

@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -104,6 +104,9 @@ def lib():
         L.gmx_adamic_adar.argtypes = [vp, vp, C.POINTER(Stats)]
         L.gmx_v_cover.argtypes = [vp, vp, C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_random_bipartite_matching.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(Stats)]
+        L.gmx_random_walk_sampling.argtypes = [vp, C.c_float, C.c_float, i32, i32, C.POINTER(C.c_uint64), vp, vp, C.POINTER(i64), C.POINTER(i32),
+                                               C.POINTER(Stats)]
+        L.gmx_node_sampling.argtypes = [vp, C.c_int, i32, C.POINTER(C.c_uint64), vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_bfs_levels.argtypes = [vp, i32, vp, C.POINTER(i32)]
         L.gmx_bc.argtypes = [vp, vp, i32, C.c_int, vp, C.POINTER(Stats)]
         L.gmx_bc_batch.argtypes = [vp, vp, i32, C.c_int, i32, vp, C.POINTER(Stats)]
@@ -555,6 +558,25 @@ class Graph:
         _ck(lib().gmx_random_bipartite_matching(self._h, left.ctypes.data if self.V else None, match.ctypes.data if self.V else None,
                                                 C.byref(cnt), C.byref(st)))
         return match[:self.V], int(cnt.value), st.as_dict()
+
+    def random_walk_sampling(self, p_size, p_jump, num_tokens, rng_state, max_rounds=INT_MAX):
+        """parallel_random_walk_jump_sampling(G, p_size, p_jump, num_tokens, Selected) as one thread of the reference runs it on
+        the 48-bit stream that starts at rng_state -- returns (selected[uint8, V], token[int32, V], count, rounds, state after,
+        stats).  Forward CSR only, any row order."""
+        sel = np.zeros(max(self.V, 1), np.uint8)
+        tok = np.zeros(max(self.V, 1), np.int32)
+        x, cnt, rounds, st = C.c_uint64(rng_state), C.c_int64(0), C.c_int32(0), Stats()
+        _ck(lib().gmx_random_walk_sampling(self._h, p_size, p_jump, num_tokens, max_rounds, C.byref(x), sel.ctypes.data, tok.ctypes.data,
+                                           C.byref(cnt), C.byref(rounds), C.byref(st)))
+        return sel[:self.V], tok[:self.V], int(cnt.value), int(rounds.value), int(x.value), st.as_dict()
+
+    def node_sampling(self, by_degree, N, rng_state):
+        """random_node_sampling (by_degree = 0) / random_degree_node_sampling (by_degree = 1): vertex v takes draw v + 1 of
+        the stream -- returns (selected[uint8, V], count, state after, stats)."""
+        sel = np.zeros(max(self.V, 1), np.uint8)
+        x, cnt, st = C.c_uint64(rng_state), C.c_int64(0), Stats()
+        _ck(lib().gmx_node_sampling(self._h, 1 if by_degree else 0, N, C.byref(x), sel.ctypes.data if self.V else None, C.byref(cnt), C.byref(st)))
+        return sel[:self.V], int(cnt.value), int(x.value), st.as_dict()
 
     def triangle_counting(self, part=0, nparts=1):
         """triangle_counting(G) -- returns (T, stats); with nparts > 1 the share of one part of the edge slots."""

@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge and gmx_v_cover's select are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -568,6 +568,59 @@ int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host /* [E], uploaded slots, 0/1
  * first to the last launch. */
 int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_left_host /* [V], 0/1 */,
                                   gmx_node_t* match_host /* [V], partner or -1 */, int32_t* count, gmx_stats_t* stats);
+
+/* ---- the sampling programs (apps/src/parallel_random_walk_jump_sampling.gm, random_node_sampling.gm,
+ * random_degree_node_sampling.gm; gmx_walk.hip) ----
+ * The stream.  Every entry below takes uint64_t* rng_state in and out: a 48-bit state x.  A draw is
+ *     x = (0x5DEECE66D * x + 0xB) mod 2^48,   u = x / 2^48 as a double
+ * which is exactly what erand48 returns.  Uniform() is one draw, PickRandom() is (node_t)(u * (double) V) and
+ * n.PickRandomNbr() is node_idx[begin[n] + (edge_t)(u * (double) deg(n))] on the rows as stored on the device (what
+ * gmx_graph_download returns).  On return *rng_state is the state after the last draw the program run by ONE thread
+ * consumed, so consecutive calls continue one stream.  The host shim's gm_rt_uniform(0) is the same stream; its state
+ * after gm_rt_set_num_threads(1) is 0x0AA849495101.
+ * Not reproduced from the reference: its pick_random_node() draws from libc rand(), which is not a portable stream, and
+ * its pick_random_out_neighbor() returns node_idx[begin[node]] + rand() % outCount, which adds the offset to a vertex id
+ * (gm_graph.h:379-391).
+ *
+ * gmx_random_walk_sampling: parallel_random_walk_jump_sampling(G, p_size, p_jump, num_tokens; Selected), as one thread runs it:
+ *     Token = TokenNxt = 0; Selected = False
+ *     S = {}; do { S.add(PickRandom()) } while (|S| < num_tokens);  Token[n] = 1 for n in S
+ *     N = (int64)((float) V * p_size)                  -- a float multiply, as the emitted C++ does
+ *     count = 0
+ *     while (count < N && rounds < max_rounds):
+ *       for n = 0 .. V-1 with Token[n] > 0:
+ *         if (!Selected[n]) { Selected[n] = True; count++ }
+ *         Token[n] times:  jump = (deg(n) == 0) || (Uniform() < (double) p_jump)      -- no draw when deg(n) == 0
+ *                          m = jump ? PickRandom() : n.PickRandomNbr();  TokenNxt[m]++
+ *       Token = TokenNxt; TokenNxt = 0; rounds++
+ * selected_host, token_host (the final Token; may be NULL), *count, *rounds and *rng_state are byte-identical to that loop,
+ * whatever the knobs below say.  max_rounds is ours: with p_jump = 0 on a closed component the reference never returns
+ * (the drop-in passes INT32_MAX).  N <= 0: the tokens are placed, no round runs, Selected is all false.
+ * GMX_ERR_ARG, with nothing written: num_tokens < 1 or > V (the reference loops for ever above V), p_size or p_jump not a
+ * number, N > V, max_rounds < 0, V = 0, or g, rng_state, selected_host, count or rounds NULL.
+ * Only the forward CSR is read, rows in any order, repeats and self loops included.  Read at every call, the results do
+ * not depend on them:
+ *   GMX_RW_TAIL   with at most this many tokens one workgroup runs the rounds, up to 1024 per launch (0: never; huge: always),
+ *   GMX_RW_ORDER  sort | dense | auto: how a grid round brings the vertices it touched into ascending order,
+ *   GMX_RW_LOG=1  one stderr line per call: V, tokens, the threshold, batches of the initial set, rounds grid + tail, tail
+ *                 launches, sort rounds, dense rounds (the ordering of the initial set counts, the last round needs none), draws,
+ *                 count, ms (2: before it a line per grid round / tail launch).
+ * stats: iterations = *rounds, vertices_reached = *count, edges_examined = tokens moved over all rounds, kernel_ms = device
+ * time from the first to the last launch, d2h_ms = the downloads. */
+int gmx_random_walk_sampling(gmx_graph_t* g, float p_size, float p_jump, int32_t num_tokens, int32_t max_rounds,
+                             uint64_t* rng_state, uint8_t* selected_host /* [V] */, int32_t* token_host /* [V] or NULL */,
+                             int64_t* count, int32_t* rounds, gmx_stats_t* stats);
+
+/* random_node_sampling(G, N; S) (by_degree = 0) and random_degree_node_sampling(G, N; S) (by_degree = 1): vertex v takes
+ * draw v + 1 of the stream as dice and is selected when
+ *     dice < 1 / (double) N                                             (by_degree = 0)
+ *     dice < ((double) deg(v) / (double) degSum) * (double) N           (by_degree = 1; degSum = E as int64)
+ * evaluated literally in IEEE double: E = 0 gives NaN and so the empty set, N = 0 without degrees gives every vertex.
+ * The state advances by V.  selected_host[v] = 0/1, *count = the vertices selected.  One kernel; forward CSR only.
+ * g, rng_state or count NULL, or selected_host NULL with V > 0: GMX_ERR_ARG.  V = 0: GMX_OK, *count = 0, state unchanged.
+ * stats: iterations = 1, vertices_reached = *count, edges_examined = V, kernel_ms, d2h_ms. */
+int gmx_node_sampling(gmx_graph_t* g, int by_degree, int32_t N, uint64_t* rng_state, uint8_t* selected_host /* [V] */,
+                      int64_t* count, gmx_stats_t* stats);
 
 /* ---- device-resident PageRank stepping (bench.py / multi-GPU driver) ----
  * A gmx_pr_t owns the rows [row_lo,row_hi) of the (internally relabelled) graph
