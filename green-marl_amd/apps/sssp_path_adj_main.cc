@@ -1,6 +1,6 @@
 // sssp_path_adj_main.cc -- route query between two vertices with double edge costs.  The reference's driver
-// (apps/output_cpp/src/sssp_path_adj_main.cc) reads an adjacency-list file with costs and edge keys, which the
-// host library here does not load: this driver is this tree's own, on the command line of the others,
+// (apps/output_cpp/src/sssp_path_adj_main.cc) reads an adjacency-list file with costs and edge keys, through the Avro
+// loader too, which the host library here does not have: this driver is this tree's own, on the command line of the others,
 //     sssp_path_adj <graph_name> <num_threads> <nfspath> <root> <end>
 // with costs ((rand() % 100) + 1) / 10.0 drawn from gm_rand32 in slot order, and prints the reference driver's report
 // (:114-139) with vertex ids for node keys and the edge slot for the edge key: `PATH NOT FOUND`, or `<root> -> <end>`,

@@ -6,7 +6,9 @@
 // sum, so one index load serves W seeds, a gather of lvl[w][.] or sd[w][.] is a fully used line, and the serial chain of float
 // adds that the contract demands (every Sum in row-slot order) runs in W lanes side by side.
 //
-// Per batch: W traversals (the existing one, through gmx_bfs_reach) staged as bytes and transposed once; then one forward pass
+// Per batch: W traversals (the existing one, through gmx_bfs_reach) staged as bytes and transposed once -- or, with
+// GMX_BCB_MSBFS and for gmx_bc_all (comp_BC of bc_adj.gm: every vertex a source; DESIGN.md 4.2g'), one bit-parallel
+// multi-source traversal that writes the same bytes; then one forward pass
 // per level from the roots (sigma) and one reverse pass per level from the deepest (delta), each a launch of its own -- every
 // value a pass reads was written by an earlier launch, nothing is read and written in one launch -- and BC[v] += delta[v][b]
 // for b ascending, which is the per-seed order of the emission.  A pass's rows come from a per-vertex (min, max) level pair
@@ -98,6 +100,215 @@ bcb_transpose_kernel(const uint32_t* __restrict__ stage, int64_t V, int64_t pitc
         }
         minmax[v0 + t] = (uint16_t) (mx << 8 | mn);
     }
+}
+
+// ---------------------------------------------------------------- levels, all columns at once (GMX_BCB_MSBFS, gmx_bc_all)
+// A bit-parallel multi-source traversal over the reverse CSR: per vertex one word of W bits in each of seen / front / next
+// (bit b = column b; 64-bit words for W = 64, 32-bit ones below), carved out of the V * W bytes the staged levels take.
+// A level is a pull: a vertex that still lacks a column ORs front[] over its reverse row, keeps the bits it has not seen,
+// and writes only its own words, its own level bytes and its own minmax -- front[] of the others is written by no
+// kernel of that level, so nothing is read and written in one launch and there is no atomic on the state.  The bytes are
+// the staged path's because BFS levels are unique.  Rows shorter than GMX_BCB_MS_LONG_MIN slots are walked by their
+// owner's lane (msb_level_kernel), the others are listed and walked by a wave each (msb_long_kernel); both stop once
+// every missing column is covered.  Only the columns whose front is not empty can be found: a level ORs the words it
+// writes into the next level's `active` word (one atomic per workgroup, read by the next launch), and a vertex that
+// misses none of those skips its row -- a source that reaches little stops costing row walks once its front is empty.
+template <int W> struct msb_word { typedef uint32_t type; };
+template <> struct msb_word<64> { typedef uint64_t type; };
+
+#define MSB_SHORT_UNROLL 4   // slots of a short row in flight per lane
+#define MSB_LONG_UNROLL 4    // 64-slot pieces of a long row in flight per wave, then one cross-lane OR and the exit test
+enum { MSB_ROWS_SHORT = 0, MSB_ROWS_LONG = 1, MSB_SLOTS = 2, MSB_SATURATED = 3, MSB_STATS = 4 };   // then found[level], then active[level]
+#define MSB_ACTIVE (MSB_STATS + BCB_DEPTH_CAP + 2)   // active[l]: the columns with a vertex in level l's front (the OR of its words)
+#define MSB_TALLY (MSB_ACTIVE + BCB_DEPTH_CAP + 3)
+
+__device__ __forceinline__ int msb_popc(uint32_t x) { return __popc(x); }
+__device__ __forceinline__ int msb_popc(uint64_t x) { return __popcll(x); }
+__device__ __forceinline__ uint32_t msb_wave_or(uint32_t x) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) x |= (uint32_t) __shfl_xor((int) x, d, 64);
+    return x;
+}
+__device__ __forceinline__ uint64_t msb_wave_or(uint64_t x) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) x |= (uint64_t) __shfl_xor((unsigned long long) x, d, 64);
+    return x;
+}
+
+// a workgroup's counters into the batch's tally, and the columns it found into the next level's active word: one atomic
+// per workgroup and non-zero value (s_t: MSB_STATS counters, the new pairs, the new columns)
+__device__ __forceinline__ void msb_tally(unsigned long long* s_t, unsigned long long* __restrict__ tally, int32_t l, unsigned long long rows, int which,
+                                          unsigned long long slots, unsigned long long sat, unsigned long long pairs, unsigned long long columns) {
+    if (rows) atomicAdd(&s_t[which], rows);
+    if (slots) atomicAdd(&s_t[MSB_SLOTS], slots);
+    if (sat) atomicAdd(&s_t[MSB_SATURATED], sat);
+    if (pairs) atomicAdd(&s_t[MSB_STATS], pairs);
+    columns = msb_wave_or((uint64_t) columns);
+    if ((threadIdx.x & 63) == 0 && columns) atomicOr(&s_t[MSB_STATS + 1], columns);
+    __syncthreads();
+    if (threadIdx.x <= MSB_STATS && s_t[threadIdx.x]) atomicAdd(&tally[threadIdx.x == MSB_STATS ? MSB_STATS + l : (int) threadIdx.x], s_t[threadIdx.x]);
+    if (threadIdx.x == MSB_STATS + 1 && s_t[threadIdx.x]) atomicOr(&tally[MSB_ACTIVE + l + 1], s_t[threadIdx.x]);
+}
+
+// everything unreached; the mask words clear
+template <int W>
+__global__ void __launch_bounds__(BFS_THREADS)
+msb_clear_kernel(int64_t V, typename msb_word<W>::type* __restrict__ seen, typename msb_word<W>::type* __restrict__ front, uint32_t* __restrict__ lvl, uint16_t* __restrict__ minmax) {
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < V * (W / 4); i += stride) lvl[i] = 0xFFFFFFFFu;
+    for (int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; v < V; v += stride) {
+        seen[v] = 0;
+        front[v] = 0;
+        minmax[v] = 0x00FFu;
+    }
+}
+
+// level 0: one wave, lane b = column b.  Duplicate seeds are independent columns on one vertex: every lane of that vertex
+// gathers all its columns' bits and the lanes store the same word
+template <int W>
+__global__ void __launch_bounds__(64)
+msb_seed_kernel(const int32_t* __restrict__ seeds, int32_t nb, typename msb_word<W>::type* __restrict__ seen, typename msb_word<W>::type* __restrict__ front,
+                uint8_t* __restrict__ lvl, uint16_t* __restrict__ minmax, unsigned long long* __restrict__ tally) {
+    typedef typename msb_word<W>::type word;
+    const int b = threadIdx.x;
+    const int32_t mine = b < nb ? seeds[b] : -1;
+    word m = 0;
+    for (int j = 0; j < nb; j++) {   // (wave-uniform)
+        const int32_t other = __shfl(mine, j, 64);
+        if (other == mine) m |= (word) 1 << j;
+    }
+    if (b < nb) {
+        seen[mine] = m;
+        front[mine] = m;
+        lvl[(int64_t) mine * W + b] = 0;
+        minmax[mine] = 0;
+    }
+    if (b == 0) tally[MSB_ACTIVE + 1] = nb >= 64 ? ~0ull : (1ull << nb) - 1;   // every column has its root in level 1's front
+}
+
+// what a vertex does with the columns a level found for it (its own words and bytes only)
+template <int W>
+__device__ __forceinline__ void msb_settle(int64_t v, typename msb_word<W>::type s, typename msb_word<W>::type nw, int32_t l, bool store,
+                                           typename msb_word<W>::type* __restrict__ seen, uint16_t* __restrict__ minmax) {
+    if (!nw) return;
+    seen[v] = s | nw;
+    if (store) {
+        const uint32_t mn = minmax[v] & 0xFFu;   // levels ascend: the first one found is the shallowest
+        minmax[v] = (uint16_t) ((uint32_t) l << 8 | (mn == BCB_UNREACHED ? (uint32_t) l : mn));
+    }
+}
+
+// level l, every vertex: saturated ones (no column missing whose front is not empty: the others can find nothing) only clear
+// their next word; rows of at least long_min slots go to long_list (one append per wave); the others are walked here.  store = 0 is the probe of the level past the depth
+// cap: it says whether that level is empty and stores no level byte
+template <int W>
+__global__ void __launch_bounds__(BFS_THREADS)
+msb_level_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ idx, int64_t V, typename msb_word<W>::type live, int32_t l, int32_t long_min, int store,
+                 typename msb_word<W>::type* __restrict__ seen, const typename msb_word<W>::type* __restrict__ front, typename msb_word<W>::type* __restrict__ next,
+                 uint8_t* __restrict__ lvl, uint16_t* __restrict__ minmax, int32_t* __restrict__ long_list, unsigned int* __restrict__ long_count,
+                 unsigned long long* __restrict__ tally) {
+    typedef typename msb_word<W>::type word;
+    __shared__ unsigned long long s_t[MSB_STATS + 2];
+    if (threadIdx.x <= MSB_STATS + 1) s_t[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned long long rows = 0, slots = 0, sat = 0, pairs = 0;
+    word columns = 0;
+    const word active = live & (word) tally[MSB_ACTIVE + l];
+    const int lane = threadIdx.x & 63;
+    for (int64_t v0 = (int64_t) blockIdx.x * BFS_THREADS; v0 < V; v0 += (int64_t) gridDim.x * BFS_THREADS) {   // (workgroup-uniform)
+        const int64_t v = v0 + threadIdx.x;
+        word s = 0, unseen = 0;
+        int32_t rb = 0, re = 0;
+        if (v < V) {
+            s = seen[v];
+            unseen = active & ~s;
+            if (unseen) {
+                rb = begin[v];
+                re = begin[v + 1];
+            } else {
+                sat++;
+                next[v] = 0;
+            }
+        }
+        const bool is_long = unseen && (re - rb >= long_min || long_min <= 1);
+        const unsigned long long votes = __ballot(is_long);
+        if (votes) {
+            unsigned int base = 0;
+            if (lane == __ffsll((long long) votes) - 1) base = atomicAdd(long_count, (unsigned int) __popcll(votes));
+            base = (unsigned int) __shfl((int) base, __ffsll((long long) votes) - 1, 64);
+            if (is_long) long_list[base + __popcll(votes & ((1ull << lane) - 1))] = (int32_t) v;
+        }
+        if (!unseen || is_long) continue;
+        word acc = 0;
+        int32_t e = rb;
+        for (; e + MSB_SHORT_UNROLL <= re && (acc & unseen) != unseen; e += MSB_SHORT_UNROLL) {
+            int32_t w[MSB_SHORT_UNROLL];
+#pragma unroll
+            for (int j = 0; j < MSB_SHORT_UNROLL; j++) w[j] = idx[e + j];
+#pragma unroll
+            for (int j = 0; j < MSB_SHORT_UNROLL; j++) acc |= front[w[j]];
+        }
+        for (; e < re && (acc & unseen) != unseen; e++) acc |= front[idx[e]];
+        rows++;
+        slots += (unsigned long long) (e - rb);
+        const word nw = acc & unseen;
+        next[v] = nw;
+        msb_settle<W>(v, s, nw, l, store != 0, seen, minmax);
+        pairs += (unsigned long long) msb_popc(nw);
+        columns |= nw;
+        if (store)
+            for (word left = nw; left; left &= left - 1) lvl[v * W + (msb_popc((word) ((left & (~left + 1)) - 1)))] = (uint8_t) l;
+    }
+    msb_tally(s_t, tally, l, rows, MSB_ROWS_SHORT, slots, sat, pairs, columns);
+}
+
+// level l, the listed rows: a wave per row, lane = slot, MSB_LONG_UNROLL pieces of 64 slots in flight, then the OR across the
+// lanes (order-free, so exact) and the exit test; lane b stores column b's level byte
+template <int W>
+__global__ void __launch_bounds__(BFS_THREADS)
+msb_long_kernel(const int32_t* __restrict__ list, const unsigned int* __restrict__ count, const int32_t* __restrict__ begin, const int32_t* __restrict__ idx,
+                typename msb_word<W>::type live, int32_t l, int store, typename msb_word<W>::type* __restrict__ seen, const typename msb_word<W>::type* __restrict__ front,
+                typename msb_word<W>::type* __restrict__ next, uint8_t* __restrict__ lvl, uint16_t* __restrict__ minmax, unsigned long long* __restrict__ tally) {
+    typedef typename msb_word<W>::type word;
+    __shared__ unsigned long long s_t[MSB_STATS + 2];
+    if (threadIdx.x <= MSB_STATS + 1) s_t[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned long long rows = 0, slots = 0, pairs = 0;
+    word columns = 0;
+    const word active = live & (word) tally[MSB_ACTIVE + l];
+    const int lane = threadIdx.x & 63;
+    const unsigned int n = *count, nwaves = gridDim.x * (BFS_THREADS >> 6);
+    for (unsigned int k = blockIdx.x * (BFS_THREADS >> 6) + (threadIdx.x >> 6); k < n; k += nwaves) {   // (wave-uniform)
+        const int64_t v = list[k];
+        const int32_t rb = begin[v], re = begin[v + 1];
+        const word s = seen[v], unseen = active & ~s;
+        word acc = 0;
+        int32_t base = rb;
+        while (base < re) {
+            word f[MSB_LONG_UNROLL];
+#pragma unroll
+            for (int j = 0; j < MSB_LONG_UNROLL; j++) {
+                const int32_t e = base + 64 * j + lane;
+                f[j] = e < re ? front[idx[e]] : (word) 0;
+            }
+#pragma unroll
+            for (int j = 0; j < MSB_LONG_UNROLL; j++) acc |= f[j];
+            acc = msb_wave_or(acc);
+            base = re - base > 64 * MSB_LONG_UNROLL ? base + 64 * MSB_LONG_UNROLL : re;
+            if ((acc & unseen) == unseen) break;
+        }
+        const word nw = acc & unseen;
+        if (store && lane < W && ((nw >> lane) & 1)) lvl[v * W + lane] = (uint8_t) l;
+        if (lane == 0) {
+            next[v] = nw;
+            msb_settle<W>(v, s, nw, l, store != 0, seen, minmax);
+            rows++;
+            slots += (unsigned long long) (base - rb);
+            pairs += (unsigned long long) msb_popc(nw);
+            columns |= nw;
+        }
+    }
+    msb_tally(s_t, tally, l, rows, MSB_ROWS_LONG, slots, 0, pairs, columns);
 }
 
 // s.sigma = 1 of every column (with skip_root the root is not visited and keeps it; without, pass 0 overwrites it with an
@@ -326,9 +537,65 @@ static void bcb_trace(bool on, int64_t batch, int32_t nb, int W, int32_t depth, 
 }
 
 struct bcb_knobs {
-    int32_t max_depth, long_min;
-    bool trace;
+    int32_t max_depth, long_min, ms_long_min;
+    bool trace, msbfs;
 };
+
+// The levels of one batch by the multi-source traversal: lvl, minmax, the deepest level and the reached (vertex, column)
+// pairs, roots included.  One host synchronisation per level (the level's count of new pairs).  *batched = false: level
+// max_depth + 1 is not empty (no byte of it was stored); the batch then runs per seed.  `masks` is the stage buffer.
+template <int W>
+static int bcb_msbfs(gmx_graph* g, const int32_t* seeds_dev, int32_t nb, const bcb_knobs& kn, void* masks, uint32_t* lvl, uint16_t* minmax, int32_t* long_list,
+                     unsigned int* long_counts, unsigned long long* tally, int32_t* deepest_out, int64_t* reached_out, bool* batched_out) {
+    typedef typename msb_word<W>::type word;
+    const int64_t V = g->V;
+    word* seen = (word*) masks;
+    word* front = seen + V;
+    word* next = front + V;
+    const word live = nb >= W ? ~(word) 0 : (word) (((word) 1 << nb) - 1);
+    const int level_grid = grid_for(V, BFS_THREADS, 256 * 8);
+    const int long_grid = grid_for(V, BFS_THREADS >> 6, 256 * 8);
+    GMX_HIP(hipMemsetAsync(tally, 0, sizeof(unsigned long long) * MSB_TALLY, 0));
+    GMX_HIP(hipMemsetAsync(long_counts, 0, sizeof(unsigned int) * (BCB_DEPTH_CAP + 2), 0));
+    hipLaunchKernelGGL((msb_clear_kernel<W>), dim3(grid_for(V * (W / 4))), dim3(BFS_THREADS), 0, 0, V, seen, front, lvl, minmax);
+    hipLaunchKernelGGL((msb_seed_kernel<W>), dim3(1), dim3(64), 0, 0, seeds_dev, nb, seen, front, (uint8_t*) lvl, minmax, tally);
+    int32_t deepest = 0;
+    int64_t reached = nb;
+    bool batched = true;
+    for (int32_t l = 1;; l++) {
+        const int store = l <= kn.max_depth;
+        hipLaunchKernelGGL((msb_level_kernel<W>), dim3(level_grid), dim3(BFS_THREADS), 0, 0, (const int32_t*) g->r_begin.p, (const int32_t*) g->r_node_idx.p, V, live, l,
+                           kn.ms_long_min, store, seen, (const word*) front, next, (uint8_t*) lvl, minmax, long_list, long_counts + l, tally);
+        hipLaunchKernelGGL((msb_long_kernel<W>), dim3(long_grid), dim3(BFS_THREADS), 0, 0, (const int32_t*) long_list, (const unsigned int*) (long_counts + l),
+                           (const int32_t*) g->r_begin.p, (const int32_t*) g->r_node_idx.p, live, l, store, seen, (const word*) front, next, (uint8_t*) lvl, minmax, tally);
+        GMX_HIP(hipGetLastError());
+        unsigned long long found = 0;
+        GMX_HIP(hipMemcpy(&found, tally + MSB_STATS + l, sizeof(found), hipMemcpyDeviceToHost));
+        if (!found) break;
+        deepest = l;
+        if (!store) {   // deeper than the cap (l = max_depth + 1 <= 255)
+            batched = false;
+            break;
+        }
+        reached += (int64_t) found;
+        word* t = front;
+        front = next;
+        next = t;
+    }
+    *deepest_out = deepest;
+    *reached_out = reached;
+    *batched_out = batched;
+    return GMX_OK;
+}
+
+static int bcb_msbfs_trace(bool on, int64_t batch, int32_t levels, const unsigned long long* tally) {
+    if (!on) return GMX_OK;
+    unsigned long long h[MSB_STATS];
+    GMX_HIP(hipMemcpy(h, tally, sizeof(h), hipMemcpyDeviceToHost));
+    fprintf(stderr, "gmx bc_batch msbfs batch %lld: levels %d rows %llu short + %llu long slots %llu saturated %llu\n", (long long) batch, levels, h[MSB_ROWS_SHORT],
+            h[MSB_ROWS_LONG], h[MSB_SLOTS], h[MSB_SATURATED]);
+    return GMX_OK;
+}
 
 // the batches of width W; bc (device) is zeroed and then accumulates in seed order.  `started` is recorded once the work
 // buffers exist (no allocation after it)
@@ -343,6 +610,7 @@ static int bcb_run(gmx_graph* g, const gmx_node_t* seeds, const int32_t* seeds_d
     dbuf<int32_t> short_list, long_list, depth;
     dbuf<unsigned int> counts;             // [pass][2] rows listed
     dbuf<unsigned long long> tally;        // [0] slots walked, [1 + b] vertices column b reaches
+    dbuf<unsigned long long> ms_tally;     // the multi-source traversal's counters: MSB_STATS of them, then the new pairs of every level
     GMX_CHECK(sd.alloc((size_t) V * W));
     GMX_CHECK(lvl.alloc((size_t) V * (W / 4)));
     GMX_CHECK(stage.alloc((size_t) pitch_words * W));
@@ -352,6 +620,7 @@ static int bcb_run(gmx_graph* g, const gmx_node_t* seeds, const int32_t* seeds_d
     GMX_CHECK(depth.alloc(W));
     GMX_CHECK(counts.alloc(2 * BCB_MAX_PASSES));
     GMX_CHECK(tally.alloc(1 + W));
+    if (kn.msbfs) GMX_CHECK(ms_tally.alloc(MSB_TALLY));
     std::vector<unsigned int> h_counts(2 * BCB_MAX_PASSES);
     GMX_HIP(hipEventRecord(started, 0));
     GMX_HIP(hipMemsetAsync(bc, 0, sizeof(float) * (size_t) V, 0));   // G.BC = 0
@@ -369,7 +638,8 @@ static int bcb_run(gmx_graph* g, const gmx_node_t* seeds, const int32_t* seeds_d
         int32_t deepest = 0;
         int64_t batch_reached = 0;
         bool batched = true;
-        for (int32_t b = 0; b < nb && batched; b++) {
+        if (kn.msbfs) GMX_CHECK(bcb_msbfs<W>(g, seeds_dev + off, nb, kn, stage.p, lvl.p, minmax.p, long_list.p, counts.p, ms_tally.p, &deepest, &batch_reached, &batched));
+        for (int32_t b = 0; b < nb && batched && !kn.msbfs; b++) {
             const int32_t* dist = nullptr;
             int64_t edges = 0;
             GMX_CHECK(gmx_bfs_reach(g, seeds[off + b], &dist, &edges));
@@ -387,10 +657,11 @@ static int bcb_run(gmx_graph* g, const gmx_node_t* seeds, const int32_t* seeds_d
             GMX_CHECK(gmx_bc_seeds(g, seeds + off, nb, skip_root, bc, false, nullptr, &batch_reached));
             reached += batch_reached;
             bcb_trace(kn.trace, batch, nb, W, deepest, false, tot);
+            if (kn.msbfs) GMX_CHECK(bcb_msbfs_trace(kn.trace, batch, deepest, ms_tally.p));
             continue;
         }
         reached += batch_reached;
-        hipLaunchKernelGGL((bcb_transpose_kernel<W>), dim3(vblocks), dim3(256), 0, 0, (const uint32_t*) stage.p, V, pitch_words, nb, lvl.p, minmax.p);
+        if (!kn.msbfs) hipLaunchKernelGGL((bcb_transpose_kernel<W>), dim3(vblocks), dim3(256), 0, 0, (const uint32_t*) stage.p, V, pitch_words, nb, lvl.p, minmax.p);
         hipLaunchKernelGGL(bcb_seed_kernel, dim3(1), dim3(64), 0, 0, sd.p, seeds_dev + off, nb, W);
         const int32_t l0 = skip_root ? 1 : 0;   // with skip_root the roots (level 0 of their column) are not visited
         const int32_t npass = deepest >= l0 ? 2 * (deepest - l0 + 1) : 0;
@@ -428,6 +699,7 @@ static int bcb_run(gmx_graph* g, const gmx_node_t* seeds, const int32_t* seeds_d
             }
             tot.slots = (long long) batch_slots;
             bcb_trace(true, batch, nb, W, deepest, true, tot);
+            if (kn.msbfs) GMX_CHECK(bcb_msbfs_trace(true, batch, deepest, ms_tally.p));
         }
     }
     *reached_out = reached;
@@ -437,18 +709,15 @@ static int bcb_run(gmx_graph* g, const gmx_node_t* seeds, const int32_t* seeds_d
 
 #define BCB_DEFAULT_WIDTH 64   // width = 0 without GMX_BCB_WIDTH: the best median at RMAT-24 (the measured table)
 
-extern "C" int gmx_bc_batch(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, int32_t width, float* bc_host, gmx_stats_t* stats) {
-    GMX_REQUIRE(g && bc_host && (seeds || nseeds == 0) && nseeds >= 0, "bad argument");
-    GMX_REQUIRE(width == 0 || width == 1 || width == 16 || width == 32 || width == 64, "width %d: 0, 1, 16, 32 or 64", width);
-    GMX_REQUIRE(g->has_reverse, "comp_BC needs the reverse CSR (UpNbrs)");
-    if (stats) memset(stats, 0, sizeof(*stats));
+// gmx_bc_batch and gmx_bc_all behind their argument checks; msbfs_default: GMX_BCB_MSBFS when the environment does not set it
+static int bcb_call(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, int32_t width, float* bc_host, gmx_stats_t* stats, int msbfs_default) {
     const int64_t V = g->V;
-    if (V == 0) return GMX_OK;
-    for (int32_t i = 0; i < nseeds; i++) GMX_REQUIRE(seeds[i] >= 0 && seeds[i] < V, "seed %d out of range", seeds[i]);
     bcb_knobs kn;
     kn.max_depth = (int32_t) gmx_env_int("GMX_BCB_MAX_DEPTH", BCB_DEPTH_CAP, 0, BCB_DEPTH_CAP);   // (the environment lowers it, never raises it)
     kn.long_min = (int32_t) gmx_env_int("GMX_BCB_LONG_MIN", 256, 1, INT_MAX);
     kn.trace = gmx_env_int("GMX_BCB_TRACE", 0, 0, 1) != 0;
+    kn.msbfs = gmx_env_int("GMX_BCB_MSBFS", msbfs_default, 0, 1) != 0;
+    kn.ms_long_min = (int32_t) gmx_env_int("GMX_BCB_MS_LONG_MIN", 256, 1, INT_MAX);
     int W = width;
     if (W == 0) {
         W = (int) gmx_env_int("GMX_BCB_WIDTH", BCB_DEFAULT_WIDTH, 0, 1 << 20);
@@ -492,6 +761,29 @@ extern "C" int gmx_bc_batch(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nse
         stats->edges_examined = slots;
     }
     return GMX_OK;
+}
+
+extern "C" int gmx_bc_batch(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, int32_t width, float* bc_host, gmx_stats_t* stats) {
+    GMX_REQUIRE(g && bc_host && (seeds || nseeds == 0) && nseeds >= 0, "bad argument");
+    GMX_REQUIRE(width == 0 || width == 1 || width == 16 || width == 32 || width == 64, "width %d: 0, 1, 16, 32 or 64", width);
+    GMX_REQUIRE(g->has_reverse, "comp_BC needs the reverse CSR (UpNbrs)");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (g->V == 0) return GMX_OK;
+    for (int32_t i = 0; i < nseeds; i++) GMX_REQUIRE(seeds[i] >= 0 && seeds[i] < g->V, "seed %d out of range", seeds[i]);
+    return bcb_call(g, seeds, nseeds, skip_root, width, bc_host, stats, 0);
+}
+
+// comp_BC(G, BC) of bc_adj.gm: every vertex a source, in node order
+extern "C" int gmx_bc_all(gmx_graph_t* g, int skip_root, int32_t width, float* bc_host, gmx_stats_t* stats) {
+    GMX_REQUIRE(g && bc_host, "bad argument");
+    GMX_REQUIRE(width == 0 || width == 1 || width == 16 || width == 32 || width == 64, "width %d: 0, 1, 16, 32 or 64", width);
+    GMX_REQUIRE(g->has_reverse, "comp_BC needs the reverse CSR (UpNbrs)");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (g->V == 0) return GMX_OK;
+    GMX_REQUIRE(g->V <= INT32_MAX, "too many vertices");
+    std::vector<gmx_node_t> seeds((size_t) g->V);
+    for (int64_t v = 0; v < g->V; v++) seeds[(size_t) v] = (gmx_node_t) v;
+    return bcb_call(g, seeds.data(), (int32_t) g->V, skip_root, width, bc_host, stats, 1);
 }
 
 void gmx_touch_bc_batch() {

@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <unordered_map>
 #include <vector>
 
 #include "gm_graph_typedef.h"
@@ -87,6 +88,32 @@ class gm_graph
     bool store_binary(char* filename);
     bool load_binary(char* filename);   // also semi-sorts and builds reverse edges, like the reference
 
+    // ---- adjacency-list text format (gm_graph_adj_loader.cc:112-219) ----
+    // A line is `key {vertex values} [dst-key {edge values}]*`, split at any character of `separators`; lines without a
+    // token are skipped.  Source keys become node ids in order of appearance; keys that occur only as destinations follow
+    // in ascending key order with zero / false vertex values.  Rows are semi-sorted and the reverse edges built.  One
+    // new[] array of the schema's C type (bool, int, long, float, double) is appended to vertex_props / edge_props per
+    // schema entry, the edge arrays in sorted-slot order (slot e holds the value read for e_idx2idx[e]); they are the
+    // caller's to delete[].  false with a message on stderr: a file that cannot be read, a line that ends inside a vertex's
+    // or an edge's values, a schema type other than those five, a key that starts two lines (the reference counts a
+    // second node for it and leaves its key table one short), use_hdfs.
+    bool load_adjacency_list(const char* filename, std::vector<VALUE_TYPE> vprop_schema, std::vector<VALUE_TYPE> eprop_schema,
+                             std::vector<void*>& vertex_props, std::vector<void*>& edge_props, const char* separators = "\t", bool use_hdfs = false);
+    // The same lines written back, rows and edge values in slot order ("%d" / "%ld" / "%f" values, "true" / "false").
+    bool store_adjacency_list(const char* filename, std::vector<VALUE_TYPE> vprop_schema, std::vector<VALUE_TYPE> eprop_schema,
+                              std::vector<void*>& vertex_props, std::vector<void*>& edge_props, const char* separators = "\t", bool use_hdfs = false);
+
+    // node keys: the identity unless the graph came from load_adjacency_list; clear_graph() drops the table.
+    // nodekey_to_nodeid of a key the table lacks is NIL_NODE (ask find_nodekey first).
+    node_t nodekey_to_nodeid(node_t key) {
+        if (!_nodekey_defined) return key;
+        std::unordered_map<node_t, node_t>::const_iterator it = _key2id.find(key);
+        return it == _key2id.end() ? NIL_NODE : it->second;
+    }
+    node_t nodeid_to_nodekey(node_t nodeid) { return _nodekey_defined ? _id2key[(size_t) nodeid] : nodeid; }
+    bool find_nodekey(node_t key) { return _nodekey_defined ? _key2id.count(key) != 0 : (key >= 0 && key < _numNodes); }
+    node_t get_num_nodekeys() { return (node_t) _key2id.size(); }
+
     // id <-> idx (node ids are their indices; edge ids are remembered across freeze)
     edge_t get_edge_idx(edge_id e) { return e_id2idx == NULL ? e : e_id2idx[e]; }
     node_t get_node_idx(node_id n) { return n; }
@@ -119,6 +146,11 @@ class gm_graph
     edge_t* e_id2idx;
     edge_t* e_idx2id;
     gmx_graph* _dev;
+    bool _nodekey_defined;
+    std::unordered_map<node_t, node_t> _key2id;
+    std::vector<node_t> _id2key;
+    node_t add_nodekey(node_t key);
+    void delete_nodekey();
 };
 
 #endif

@@ -26,7 +26,7 @@ int GM_SIZE_CHECK_VAR;
 gm_graph::gm_graph()
     : begin(NULL), node_idx(NULL), node_idx_src(NULL), r_begin(NULL), r_node_idx(NULL), r_node_idx_src(NULL),
       e_idx2idx(NULL), e_rev2idx(NULL), _numNodes(0), _numEdges(0), _reverse_edge(false), _frozen(false),
-      _directed(true), _semi_sorted(false), e_id2idx(NULL), e_idx2id(NULL), _dev(NULL) {}
+      _directed(true), _semi_sorted(false), e_id2idx(NULL), e_idx2id(NULL), _dev(NULL), _nodekey_defined(false) {}
 
 gm_graph::~gm_graph() {
     drop_device_mirror();
@@ -51,8 +51,9 @@ void gm_graph::drop_device_mirror() {
     _dev = NULL;
 }
 
-void gm_graph::clear_graph(bool) {
+void gm_graph::clear_graph(bool clean_key_id_mappings) {
     drop_device_mirror();
+    if (clean_key_id_mappings) delete_nodekey();
     _adj.clear();
     release_csr();
     _numNodes = 0;

@@ -94,7 +94,7 @@ int gmx_workspace_release(void);
  * have sorted rows.  The other uploads keep the caller's arrays verbatim (with GMX_GRAPH_NO_REVERSE: the forward ones),
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
- *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
+ *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
  *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge and gmx_v_cover's select are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
@@ -224,6 +224,22 @@ int gmx_bc(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_roo
  * slots the batched sweeps walked (0 on the per-seed path). */
 int gmx_bc_batch(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root,
                  int32_t width, float* bc_host /* [V] */, gmx_stats_t* stats);
+
+/* gmx_bc_all = comp_BC(G, BC) of apps/src/bc_adj.gm (driver apps/output_cpp/src/bc_adj_main.cc): exact betweenness
+ * centrality, every vertex a source in node order.  bc_host[V] holds the bytes of gmx_bc(g, {0, 1, .., V-1}, V, skip_root, ..);
+ * skip_root = 1 is bc_adj.gm's `(v != s)` form.  width, the argument checks, the memory rule, the depth cap, the error for a
+ * graph without its reverse CSR, the knobs, the trace and the stats are gmx_bc_batch's (iterations = V).  V = 0: GMX_OK.
+ *
+ * GMX_BCB_MSBFS (0 or 1, read at every call; default 0 for gmx_bc_batch, 1 for gmx_bc_all): the levels of a batch come
+ * from one bit-parallel multi-source traversal over the reverse CSR -- a word of `width` bits per vertex, one chain of
+ * launches and one host synchronisation per level for all columns -- in place of one traversal per seed.  Same bytes, same
+ * stats, same memory (the mask words take the place of the staged levels).  GMX_BCB_MS_LONG_MIN (default 256): reverse rows
+ * with at least that many slots are walked by a wave, shorter ones by a lane (1: every row by a wave).  With the knob on,
+ * GMX_BCB_TRACE=1 prints after each batch's line
+ *   gmx bc_batch msbfs batch <i>: levels <d> rows <s> short + <k> long slots <n> saturated <m>
+ * (rows and slots the traversal walked -- a walk stops once every missing column is covered -- and the vertex visits
+ * skipped because no column was missing whose front still held a vertex). */
+int gmx_bc_all(gmx_graph_t* g, int skip_root, int32_t width, float* bc_host /* [V] */, gmx_stats_t* stats);
 
 /* sssp(G, dist, len, root) (apps/src/sssp.gm; driver apps/output_cpp/src/sssp_main.cc:42): shortest path lengths
  * over out-edges with the caller's edge property len[E] (indexed by forward edge slot), INT_MAX = unreachable.
