@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_wcc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge and gmx_v_cover's select are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -393,6 +393,33 @@ int gmx_conduct(gmx_graph_t* g, const int32_t* member_host, int32_t num, float* 
  * trim / FW-BW / colouring rounds, vertices_reached = size of the largest SCC, edges_examined = edge slots inspected,
  * kernel_ms = device time, d2h_ms = download of comp. */
 int gmx_scc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, gmx_stats_t* stats);
+
+/* Weakly connected components (the reference has no such program): two vertices are in one component when a path joins
+ * them with every edge usable in both directions.  The result follows gmx_scc's conventions, so the two can be compared
+ * directly (on a symmetric graph they are equal): comp_host[V] = the component of every vertex, ids dense over
+ * 0 .. count-1 in increasing order of each component's smallest vertex id, *num_comps = the count.  The bytes are identical
+ * from run to run and under every knob below.
+ * g == NULL or comp_host == NULL: GMX_ERR_ARG, checked before any device call.  num_comps and stats may be NULL.  V = 0:
+ * GMX_OK with count 0.  E = 0: the identity with count V.  Self loops and repeated slots are harmless; rows are read in
+ * any order (no GMX_ERR_STATE for unsorted rows).  A GMX_GRAPH_NO_REVERSE graph is accepted and gives the same arrays: only
+ * the work differs.  Nothing is cached on the graph.
+ * The scheme is Afforest's: K sampling rounds link every vertex with its out-slots 0 .. K-1, the most
+ * frequent root g* among 1024 fixed probes names the tree to skip, and the final pass links the whole out-rows and
+ * in-rows of the vertices outside that tree -- or, without a reverse CSR, the out-rows of every vertex.
+ * stats: iterations = sampling rounds + 1, vertices_reached = size of the largest component, kernel_ms = device time from
+ * the first launch to the last (renumbering included), d2h_ms = download of comp, edges_examined = slots read: one per
+ * (vertex, round r) with outdeg(v) > r, plus every slot of every row the final pass walks (whole rows, the first K slots
+ * of an out-row that sampling already read included); without a reverse CSR or with GMX_WCC_SKIP=0 that is exactly
+ * sum_v min(K, outdeg v) + E.
+ * Read at every call, the result does not depend on them:
+ *   GMX_WCC_SAMPLE_ROUNDS  K, default 2, 0 .. 8,
+ *   GMX_WCC_SKIP           0: every vertex is live and only out-rows are walked, as without a reverse CSR,
+ *   GMX_WCC_GIANT          <vertex>: g* = that vertex's root after sampling (for tests),
+ *   GMX_WCC_LOG            one line per call on stderr: `gmx wcc: V <V> E <E> sample_rounds <K> sampled <n> giant <root>
+ *                          skipped <s> live <l> reverse <0|1> final_slots <n> comps <c> largest <m>`, with
+ *                          skipped + live = V and sampled + final_slots = edges_examined,
+ *   GMX_WCC_PHASES         the device time of the five phases on stderr (tools/wcc_prof.py). */
+int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, gmx_stats_t* stats);
 
 /* communities(G, comm) (apps/src/communities.gm:1-24; driver apps/output_cpp/src/communities_main.cc:19): label-propagation
  * community detection.  comm[x] = x; then every vertex x counts the labels of its out-neighbours, once per slot (a
