@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -121,6 +121,7 @@ def lib():
         L.gmx_bidir_dijkstra.argtypes = [vp, vp, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_scc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_wcc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_kcore.argtypes = [vp, C.c_int, vp, vp, C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_communities.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_potential_friends.argtypes = [vp, i32, i32, vp, vp, i64, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_avg_teen_cnt.argtypes = [vp, vp, i32, vp, C.POINTER(C.c_float), C.POINTER(Stats)]
@@ -459,6 +460,21 @@ class Graph:
         n, st = C.c_int64(0), Stats()
         _ck(lib().gmx_wcc(self._h, comp.ctypes.data, C.byref(n), C.byref(st)))
         return comp[:self.V], int(n.value), st.as_dict()
+
+    KCORE_MODES = {"in": 0, "out": 1, "both": 2}
+
+    def kcore(self, mode="in", layers=False):
+        """k-core decomposition -- returns (core[int32], max_core, stats), with layers=True (core, layer[int32], max_core,
+        stats).  mode "in", "out" or "both" names the slots that count as a vertex's degree; layer[v] is the round that
+        removed v under the schedule in gmx.h (GMX_KCORE_*).  Any row order; "out" and "both" need the reverse CSR."""
+        m = self.KCORE_MODES[mode] if isinstance(mode, str) else int(mode)
+        core = np.zeros(max(self.V, 1), np.int32)
+        layer = np.zeros(max(self.V, 1), np.int32) if layers else None
+        k, st = C.c_int32(0), Stats()
+        _ck(lib().gmx_kcore(self._h, m, core.ctypes.data, layer.ctypes.data if layers else None, C.byref(k), C.byref(st)))
+        if layers:
+            return core[:self.V], layer[:self.V], int(k.value), st.as_dict()
+        return core[:self.V], int(k.value), st.as_dict()
 
     def communities(self, max_rounds=1000):
         """communities(G, comm): label propagation under the canonical tie rule and schedule (gmx.h) -- returns

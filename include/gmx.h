@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_wcc, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_wcc, gmx_kcore, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge and gmx_v_cover's select are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -420,6 +420,42 @@ int gmx_scc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, gmx_stats_t*
  *                          skipped + live = V and sampled + final_slots = edges_examined,
  *   GMX_WCC_PHASES         the device time of the five phases on stderr (tools/wcc_prof.py). */
 int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, gmx_stats_t* stats);
+
+/* k-core decomposition (the reference has no such program): core numbers and the rounds of the peeling that finds them.
+ * Slots and degree: every stored slot u -> w with u != w counts once, a repeated slot counts again; self-loop slots are
+ * read but ignored.  mode names the slots that make a vertex's degree and the rows that removing it walks: */
+#define GMX_KCORE_IN   0   /* degree = in-slots;  removing v lowers the heads of v's out-row */
+#define GMX_KCORE_OUT  1   /* degree = out-slots; removing v lowers the tails of v's in-row  */
+#define GMX_KCORE_BOTH 2   /* degree = in-slots + out-slots; both rows are walked            */
+/* core_host[V]: core[v] = the largest k such that v lies in a set S whose every vertex has degree >= k, counting only slots
+ * with both ends in S.  On a symmetric graph (gmx_graph_symmetrize) IN and OUT are the k-core number of the undirected
+ * graph and BOTH is twice that.  *max_core = the largest core number.
+ * layer_host[V] (or NULL: no layer array is kept or downloaded): the round that removed v under this schedule, which fixes
+ * layer and the statistics (core is unique anyway): level k is the smallest degree among the live vertices (the first may
+ * be 0); round 0 of a level removes every live vertex of degree <= k, round r+1 those whose degree fell to <= k because of
+ * round r's removals; when a round removes nothing the next level starts; the rounds that removed something are numbered
+ * 0, 1, 2, ... across the whole run.  On a simple undirected graph layer + 1 is the "onion layer" of v, and sorting by
+ * layer gives a degeneracy ordering.  core and layer are byte-identical from run to run and under every knob below: a
+ * vertex is queued once, by the decrement that returns k + 1, and rounds are separated by a kernel boundary or a barrier.
+ * g == NULL, core_host == NULL (checked before g is touched) or a mode outside 0 .. 2: GMX_ERR_ARG before any device call.
+ * layer_host, max_core and stats may be NULL.  V = 0: GMX_OK, *max_core = 0.  Rows are read in any order.  IN reads only
+ * the forward rows and takes the in-degrees from the reverse CSR's offsets when the graph has one, otherwise from a
+ * histogram of the heads: a GMX_GRAPH_NO_REVERSE graph gives the same arrays.  OUT and BOTH need the reverse CSR:
+ * GMX_ERR_STATE without it.  A degree above INT32_MAX (BOTH only): GMX_ERR_ARG.  Nothing is cached on the graph.
+ * stats: iterations = rounds that removed something, vertices_reached = vertices with core == max_core, edges_examined =
+ * slots of the rows walked by removals (every vertex is removed once: E for IN and OUT, 2 E for BOTH), kernel_ms = device
+ * time from the first launch to the last, d2h_ms = the downloads.
+ * Read at every call, the result does not depend on them:
+ *   GMX_KCORE_TAIL    one workgroup runs the rounds (and the level scans) while the queue to expand holds at most this many
+ *                     slots (the live list at most as many entries); 0: never; default 1024,
+ *   GMX_KCORE_LOG     one line per call on stderr: `gmx kcore: V <V> E <E> mode <m> reverse <0|1> levels <l> rounds <r>
+ *                     scanned <n> grid_rounds <g> tail_rounds <t> slots <s> max_core <k> top <n>`, with grid_rounds +
+ *                     tail_rounds = rounds = iterations, slots = edges_examined, top = vertices_reached and scanned = the sum
+ *                     over the levels of the live list's length at the level's start (the list is compacted by every
+ *                     level's scan: it holds the vertices that were live after round 0 of the level before),
+ *   GMX_KCORE_PHASES  the device time of degrees, level scans, grid rounds and tail launches and the largest number of decrements
+ *                     one vertex received, on stderr (tools/kcore_prof.py). */
+int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* layer_host, int32_t* max_core, gmx_stats_t* stats);
 
 /* communities(G, comm) (apps/src/communities.gm:1-24; driver apps/output_cpp/src/communities_main.cc:19): label-propagation
  * community detection.  comm[x] = x; then every vertex x counts the labels of its out-neighbours, once per slot (a
