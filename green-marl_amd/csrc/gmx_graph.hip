@@ -399,6 +399,7 @@ void gmx_warm_modules() {
     gmx_touch_walk();
     gmx_touch_wcc();
     gmx_touch_kcore();
+    gmx_touch_msf();
 }
 
 static int check_sizes(int64_t V, int64_t E) {

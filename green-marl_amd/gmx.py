@@ -45,7 +45,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -122,6 +122,7 @@ def lib():
         L.gmx_scc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_wcc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_kcore.argtypes = [vp, C.c_int, vp, vp, C.POINTER(i32), C.POINTER(Stats)]
+        L.gmx_msf.argtypes = [vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_communities.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_potential_friends.argtypes = [vp, i32, i32, vp, vp, i64, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_avg_teen_cnt.argtypes = [vp, vp, i32, vp, C.POINTER(C.c_float), C.POINTER(Stats)]
@@ -475,6 +476,25 @@ class Graph:
         if layers:
             return core[:self.V], layer[:self.V], int(k.value), st.as_dict()
         return core[:self.V], int(k.value), st.as_dict()
+
+    def msf(self, weight=None, components=False):
+        """Minimum spanning forest of the stored slots read as undirected edges, ordered by (weight, uploaded slot) --
+        returns (in_forest[bool, E] by uploaded forward edge slot, num_edges, total_weight, stats), with components=True
+        (in_forest, num_edges, total_weight, comp[int32], num_comps, stats) where comp is numbered as wcc() numbers it.
+        weight[E] int32 by uploaded forward edge slot, or None: all 0.  Forward CSR only, any row order (gmx.h: GMX_MSF_*)."""
+        w = None
+        if weight is not None:
+            w = _i32(weight)
+            if w.shape != (self.E,):
+                raise ValueError("weight must have one entry per edge slot")
+        sel = np.zeros(max(self.E, 1), np.uint8)
+        comp = np.zeros(max(self.V, 1), np.int32) if components else None
+        ne, tw, nc, st = C.c_int64(0), C.c_int64(0), C.c_int64(0), Stats()
+        _ck(lib().gmx_msf(self._h, w.ctypes.data if w is not None and self.E else None, sel.ctypes.data if self.E else None, C.byref(ne), C.byref(tw),
+                          comp.ctypes.data if components else None, C.byref(nc), C.byref(st)))
+        if components:
+            return sel[:self.E].astype(bool), int(ne.value), int(tw.value), comp[:self.V], int(nc.value), st.as_dict()
+        return sel[:self.E].astype(bool), int(ne.value), int(tw.value), st.as_dict()
 
     def communities(self, max_rounds=1000):
         """communities(G, comm): label propagation under the canonical tie rule and schedule (gmx.h) -- returns

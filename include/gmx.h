@@ -95,8 +95,8 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_wcc, gmx_kcore, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
- *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge and gmx_v_cover's select are indexed by the stored slots);
+ *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge, gmx_v_cover's select and gmx_msf's weight and in_forest are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
  *     gm_common_neighbor_iter.h): GMX_ERR_STATE when the forward rows are not sorted.  With sorted forward rows and an
@@ -456,6 +456,39 @@ int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, gmx_stats_t*
  *   GMX_KCORE_PHASES  the device time of degrees, level scans, grid rounds and tail launches and the largest number of decrements
  *                     one vertex received, on stderr (tools/kcore_prof.py). */
 int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* layer_host, int32_t* max_core, gmx_stats_t* stats);
+
+/* Minimum spanning forest (the reference has no such program): Boruvka's algorithm in synchronous rounds.
+ * Graph read: every stored forward slot u -> w with u != w is an undirected edge {u, w} of weight weight_host[slot]
+ * (weight_host[E] by UPLOADED forward slot, as gmx_sssp's len; NULL: every weight 0); a repeated slot is another edge;
+ * self-loop slots are read and ignored.  Only the forward CSR is read, in any row order: a GMX_GRAPH_NO_REVERSE graph gives
+ * the same bytes.  Nothing is cached on the graph.
+ * Order: edges are ordered by (weight, uploaded slot), lexicographic, over the whole int32 range, negative weights
+ * included.  That is a strict total order, so the minimum spanning forest is unique: in_forest_host[E] (by uploaded slot,
+ * 0 / 1) is exactly what Kruskal's algorithm selects when it takes the slots in that order, byte-identical from run to
+ * run, under every knob below, and between an upload that kept the caller's rows and one that sorted them (the tie-break
+ * is the uploaded slot, not the device's).  weight_host == NULL: a spanning forest with ties to the lowest slot.
+ * *num_edges = the selected slots = V - *num_comps, *total_weight = their int64 sum.  comp_host[V] (or NULL: no component
+ * array is built or downloaded) and *num_comps equal gmx_wcc's, with the same canonical numbering.
+ * g == NULL, or in_forest_host == NULL with E > 0 (checked before g is touched otherwise): GMX_ERR_ARG before any device
+ * call.  The other pointers may be NULL.  V = 0 or E = 0: GMX_OK, no slot selected, comp the identity.
+ * The schedule, which fixes the statistics (the forest is unique anyway): round 0 lists every vertex that has an out-slot;
+ * a round reads every slot of every listed row; a slot is cross when its two ends lie in different trees at the round's
+ * start; every tree takes the smallest key among the cross slots that touch it, at either end; all chosen slots are
+ * selected and their trees merged; round r+1 lists the vertices that had a cross out-slot in round r, tested before round
+ * r's merges; the run ends when the list is empty or a round finds no cross slot.  At most ceil(log2 V) rounds merge.
+ * stats: iterations = rounds that merged something, edges_examined = slots read over all rounds (the last, empty round
+ * included), vertices_reached = the largest component when comp_host is given, else 0, kernel_ms = device time from the
+ * first launch to the last, h2d_ms = the weights, d2h_ms = the downloads.
+ * Read at every call, neither the result nor the statistics depend on them:
+ *   GMX_MSF_TAIL    one workgroup runs all remaining rounds once the list's rows hold at most this many slots (they never
+ *                   grow again); 0: never; default 4096,
+ *   GMX_MSF_LOG     one line per call on stderr: `gmx msf: V <V> E <E> reverse <0|1> rounds <r> grid_rounds <g> tail_rounds
+ *                   <t> slots <s> forest_edges <n> weight <w> comps <c>`, with g + t = r = iterations and slots =
+ *                   edges_examined,
+ *   GMX_MSF_PHASES  per round the device time of its three steps and the largest number of atomics one tree's word
+ *                   received, the tail launch and the finish, on stderr (tools/msf_prof.py; synchronises at every step). */
+int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_forest_host, int64_t* num_edges, int64_t* total_weight, int32_t* comp_host,
+            int64_t* num_comps, gmx_stats_t* stats);
 
 /* communities(G, comm) (apps/src/communities.gm:1-24; driver apps/output_cpp/src/communities_main.cc:19): label-propagation
  * community detection.  comm[x] = x; then every vertex x counts the labels of its out-neighbours, once per slot (a
