@@ -270,6 +270,7 @@ bool pr_cold_limb_guard(const pr_cold* c, double d, double N);
 const void* pr_cold_partial(const pr_cold* c);   // [nactive] x elem, indexed like the per-slice partial sums
 int64_t pr_cold_edges(const pr_cold* c);
 int64_t pr_cold_items(const pr_cold* c);
+void pr_cold_shape(const pr_cold* c, gmx_pr_cold_shape_t* out);   // everything but `fused` (NULL plan: zeros)
 
 // ---- whole-kernel PageRank over several GPUs from one host thread (gmx_pr_multi.hip) ----
 struct gmx_pr_multi;

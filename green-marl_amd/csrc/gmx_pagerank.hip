@@ -1575,6 +1575,7 @@ extern "C" int gmx_pr_create(gmx_graph_t* g, int elem_bytes, int rank, int nrank
                     hipLaunchKernelGGL(pr_deg_by_id_kernel, dim3(grid_for(V)), dim3(256), 0, s, (const int32_t*) perm.p, g->begin.p, V, deg_by_id.p);
                     pr_cold_params cp{elem_bytes, nranks, p->slice, p->cold_T, p->row_lo, p->sl_nactive, index_of_row.p, deg_by_id.p};
                     if ((st = pr_cold_create(cold_keys, Ec, cp, s, &p->cold))) break;
+                    if (getenv("GMX_PR_DEBUG")) fprintf(stderr, "gmx pr cold: shape: fused finish %d\n", pr_fused(p) ? 1 : 0);
                 }
                 int64_t nblk_s[PR_MAX_SLICES], blk_off[PR_MAX_SLICES + 1];
                 blk_off[0] = 0;
@@ -2384,6 +2385,13 @@ extern "C" int gmx_pr_cold_info(gmx_pr_t* p, int64_t* hot_ids, int64_t* cold_edg
     if (hot_ids) *hot_ids = p->cold ? p->cold_T : -1;
     if (cold_edges) *cold_edges = pr_cold_edges(p->cold);
     if (padded_items) *padded_items = pr_cold_items(p->cold);
+    return GMX_OK;
+}
+
+extern "C" int gmx_pr_cold_shape(gmx_pr_t* p, gmx_pr_cold_shape_t* out) {
+    GMX_REQUIRE(p && out, "NULL argument");
+    pr_cold_shape(p->cold, out);
+    out->fused = pr_fused(p) ? 1 : 0;
     return GMX_OK;
 }
 

@@ -152,6 +152,8 @@ struct pr_cold {
     int grid = 256;
     bool all_bins = false;   // every bin has items (the fused finish reaches every active row)
     std::vector<int32_t> tile_maxdeg;   // [ntiles] largest out-degree among a tile's sources (host; empty: unknown)
+    std::vector<int32_t> hvstart;       // host copy of vstart (pr_cold_shape)
+    std::vector<uint8_t> tile_mode;     // [ntiles] PRC_TM_* of the tiles that hold edges, 0xff for the others (host)
 };
 
 static int prc_grid_for(int64_t n, int block = 256) {
@@ -1466,6 +1468,7 @@ int pr_cold_create(const uint64_t* keys, int64_t Ec, const pr_cold_params& prm, 
             if (hmode[t] == PRC_TM_PAIR) { pair_edges += ne; pair_tiles++; }
             if (hmode[t] == PRC_TM_PAIR && class_density > 0 && ne >= class_density * nct) { hmode[t] = PRC_TM_CLASSED; class_tiles++; class_edges += ne; }
             else if (hmode[t] == PRC_TM_EDGE && all_classed && ne > 0) { hmode[t] = PRC_TM_SINGLES; class_tiles++; class_edges += ne; }
+            c->tile_mode.push_back(ne > 0 ? hmode[t] : (uint8_t) 0xff);
         }
         PRC_TRY(hipMemcpyAsync(mode.p, hmode.data(), hmode.size(), hipMemcpyHostToDevice, s), "copy");
         if (class_tiles == 0) continue;   // (round 1 only re-derives what it already has: cheap next to the sort)
@@ -1663,6 +1666,7 @@ int pr_cold_create(const uint64_t* keys, int64_t Ec, const pr_cold_params& prm, 
         }
         PRC_ALLOC(c->vstart, vstart.size());
         PRC_TRY(hipMemcpy(c->vstart.p, vstart.data(), sizeof(int32_t) * vstart.size(), hipMemcpyHostToDevice), "copy");
+        c->hvstart = vstart;
         int32_t slot = 0;
         c->all_bins = true;
         for (int64_t b = 0; b < c->nbins; b++) {
@@ -1713,6 +1717,15 @@ int pr_cold_create(const uint64_t* keys, int64_t Ec, const pr_cold_params& prm, 
                 (long long) class_tiles, (long long) class_edges, (long long) cg[0], (long long) cg[1], (long long) cg[2], (long long) cg[3],
                 (long long) cg[4], (long long) cg[5], (long long) np, (long long) c->npairs, (long long) c->P2, (long long) c->n1p,
                 (long long) c->n1e, (long long) c->n2, (long long) c->n3, (long long) c->nslots, c->lo_bits);
+        gmx_pr_cold_shape_t sh;
+        pr_cold_shape(c, &sh);
+        fprintf(stderr, "gmx pr cold: shape: groups by form edge/pair/E1/E2/E4/E8/H %lld/%lld/%lld/%lld/%lld/%lld/%lld, super-step masks "
+                "0x%x/0x%x/0x%x/0x%x/0x%x/0x%x/0x%x; phase-2 items sole/chunk %lld/%lld; split bins few/many %lld/%lld; tiles "
+                "edge/pair/classed/singles %lld/%lld/%lld/%lld\n", (long long) sh.groups[0], (long long) sh.groups[1], (long long) sh.groups[2],
+                (long long) sh.groups[3], (long long) sh.groups[4], (long long) sh.groups[5], (long long) sh.groups[6], sh.supersteps[0],
+                sh.supersteps[1], sh.supersteps[2], sh.supersteps[3], sh.supersteps[4], sh.supersteps[5], sh.supersteps[6],
+                (long long) sh.items2_sole, (long long) sh.items2_chunk, (long long) sh.bins_few, (long long) sh.bins_many,
+                (long long) sh.tiles_by_mode[0], (long long) sh.tiles_by_mode[1], (long long) sh.tiles_by_mode[2], (long long) sh.tiles_by_mode[3]);
     }
 done:
     if (st != GMX_OK) {
@@ -1728,6 +1741,30 @@ void pr_cold_free(pr_cold* c) { delete c; }
 const void* pr_cold_partial(const pr_cold* c) { return c ? (const void*) c->cold.p : nullptr; }
 int64_t pr_cold_edges(const pr_cold* c) { return c ? c->Ec : 0; }
 int64_t pr_cold_items(const pr_cold* c) { return c ? c->P2 : 0; }
+
+// What a step of this plan runs, from the host copies of the work lists (gmx.h: gmx_pr_cold_shape; `fused` is the caller's).
+// The segments are cut exactly as pr_cold_tile_kernel cuts them and counted as prc_pair_item / prc_class_item count them.
+void pr_cold_shape(const pr_cold* c, gmx_pr_cold_shape_t* out) {
+    memset(out, 0, sizeof(*out));
+    if (!c || c->Ec == 0) return;
+    auto seen = [&](int form, int64_t groups, int64_t nsuper) {
+        out->groups[form] += groups;
+        out->supersteps[form] |= 1u << (nsuper < 31 ? nsuper : 31);
+    };
+    for (const prc_item1& d : c->h1p) {
+        if (d.form == PRC_FORM_PAIR) { seen(PRC_FORM_PAIR, d.g1 - d.g0, (d.g1 - d.g0) / PRC_SUPER_GROUPS); continue; }
+        const int32_t* vs = c->hvstart.data() + ((int64_t) d.tile << PRC_CLS_BITS);
+        for (int cls = PRC_CL_E1; cls <= PRC_CL_H; cls++) {
+            const int32_t lo = std::max(d.g0, vs[cls]), hi = std::min(d.g1, vs[cls + 1]);
+            if (lo < hi) seen(cls + 1, hi - lo, (hi - lo) / PRC_BLK_GROUPS / (PRC_WAVES * PRC_PAIR_DEPTH));
+        }
+    }
+    for (const prc_item1& d : c->h1e) seen(PRC_FORM_EDGE, d.g1 - d.g0, 0);
+    for (const prc_item2& d : c->h2) (d.slot < 0 ? out->items2_sole : out->items2_chunk)++;
+    for (const prc_item3& d : c->h3) (d.nslots <= PRC_FEW_SLOTS ? out->bins_few : out->bins_many)++;
+    for (uint8_t m : c->tile_mode)
+        if (m <= PRC_TM_SINGLES) out->tiles_by_mode[m]++;
+}
 
 // phase 1 over the tile classes [k0, k1): per class the class-form items, then the generic pair / edge items
 template <typename S, int TILE>

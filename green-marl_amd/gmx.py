@@ -40,6 +40,16 @@ class DeviceInfo(C.Structure):
                 ("lds_bytes_per_cu", C.c_int32)]
 
 
+class PrColdShape(C.Structure):   # gmx_pr_cold_shape_t
+    _fields_ = [("groups", C.c_int64 * 7), ("supersteps", C.c_uint32 * 7), ("items2_sole", C.c_int64),
+                ("items2_chunk", C.c_int64), ("bins_few", C.c_int64), ("bins_many", C.c_int64),
+                ("tiles_by_mode", C.c_int64 * 4), ("fused", C.c_int32)]
+
+
+PR_COLD_FORMS = ("edge", "pair", "E1", "E2", "E4", "E8", "H")          # index order of groups / supersteps
+PR_COLD_TILE_MODES = ("edge", "pair", "classed", "singles")            # index order of tiles_by_mode
+
+
 EXPORTS = [
     "gmx_workspace_bytes", "gmx_workspace_release", "gmx_last_error", "gmx_device_count", "gmx_set_device", "gmx_device_info", "gmx_copy_bandwidth",
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
@@ -56,6 +66,7 @@ EXPORTS = [
     "gmx_pr_packed_info", "gmx_pr_recv_buffers", "gmx_pr_set_peers_packed", "gmx_pr_push_packed", "gmx_pr_unpack", "gmx_pr_recv_list",
     "gmx_pr_gather_classes", "gmx_pr_step_gather", "gmx_pr_push_join_chunk", "gmx_pr_gather_items",
     "gmx_pr_timing", "gmx_pr_kernel_time", "gmx_pr_kernel_name", "gmx_pr_default_options", "gmx_pr_cold_info",
+    "gmx_pr_cold_shape",
 ]
 
 _LIB = None
@@ -177,6 +188,7 @@ def lib():
         L.gmx_pr_download.argtypes = [vp, vp]
         L.gmx_pr_work.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
         L.gmx_pr_cold_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+        L.gmx_pr_cold_shape.argtypes = [vp, C.POINTER(PrColdShape)]
         L.gmx_pr_default_options.argtypes = [i64, C.c_int]
         L.gmx_pr_default_options.restype = C.c_uint32
         L.gmx_pr_timing.argtypes = [vp, C.c_int]
@@ -963,6 +975,17 @@ class PageRankState:
         t, e, p = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         _ck(lib().gmx_pr_cold_info(self._h, C.byref(t), C.byref(e), C.byref(p)))
         return {"hot_ids": t.value, "cold_edges": e.value, "padded_items": p.value}
+
+    def cold_shape(self):
+        """Which paths a step of the binned part takes (gmx_pr_cold_shape: host arithmetic on the plan's work lists).
+        groups / supersteps are keyed by form (PR_COLD_FORMS), tiles_by_mode by PR_COLD_TILE_MODES; supersteps[form] is
+        the set of whole super-step counts its phase-1 segments run (31 stands for 31 or more)."""
+        s = PrColdShape()
+        _ck(lib().gmx_pr_cold_shape(self._h, C.byref(s)))
+        return {"groups": dict(zip(PR_COLD_FORMS, s.groups)),
+                "supersteps": {f: {n for n in range(32) if m >> n & 1} for f, m in zip(PR_COLD_FORMS, s.supersteps)},
+                "items2_sole": s.items2_sole, "items2_chunk": s.items2_chunk, "bins_few": s.bins_few, "bins_many": s.bins_many,
+                "tiles_by_mode": dict(zip(PR_COLD_TILE_MODES, s.tiles_by_mode)), "fused": bool(s.fused)}
 
     def work(self):
         e, r, b = C.c_int64(0), C.c_int64(0), C.c_int64(0)

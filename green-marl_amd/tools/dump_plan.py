@@ -20,5 +20,5 @@ for elem in elems:
     st.timing(True)
     for _ in range(10):
         st.step()
-    print("elem", elem, st.kernel_time(), st.cold_info(), flush=True)
+    print("elem", elem, st.kernel_time(), st.cold_info(), st.cold_shape(), flush=True)
     st.free()

@@ -849,6 +849,21 @@ int gmx_pr_work(gmx_pr_t* p, int64_t* edges, int64_t* rows, int64_t* algorithmic
 /* The binned part of the plan (GMX_PR_COLD_PB): hot ids per rank range (-1 = no binned part, 0 = every edge is
  * binned), edges taken out of the pull sweep, and the items ((tile, row) pair sums + cell padding) phase 2 streams. */
 int gmx_pr_cold_info(gmx_pr_t* p, int64_t* hot_ids, int64_t* cold_edges, int64_t* padded_items);
+/* Which code paths a step of the binned part takes, computed on the host from the plan's work lists (no launch, no device
+ * read; all zero without a binned part).  Forms, in index order: edge, generic pair, E1, E2, E4, E8, H; tile modes: edge,
+ * pair, classed, singles.  A phase-1 SEGMENT is what one call of the prefetch loop walks: a generic pair item, or the piece
+ * of a classed item inside one class stream; a super-step is 1024 groups. */
+typedef struct gmx_pr_cold_shape {
+    int64_t groups[7];        /* tile-major groups (32 entries) the phase-1 items hold, by form */
+    uint32_t supersteps[7];   /* bit min(n, 31): some segment of the form runs n whole super-steps (edge form: bit 0 only) */
+    int64_t items2_sole;      /* phase-2 items that finish their bin themselves */
+    int64_t items2_chunk;     /* phase-2 items that are one chunk of a split bin */
+    int64_t bins_few;         /* split bins phase 3 adds with the few-slot kernel (<= 8 chunks) ... */
+    int64_t bins_many;        /* ... and with the many-slot kernel */
+    int64_t tiles_by_mode[4]; /* tiles with edges, by how they are stored */
+    int32_t fused;            /* 1: phases 2-3 apply the PageRank update themselves (every in-edge binned, every bin has items) */
+} gmx_pr_cold_shape_t;
+int gmx_pr_cold_shape(gmx_pr_t* p, gmx_pr_cold_shape_t* out);
 
 #ifdef __cplusplus
 }
