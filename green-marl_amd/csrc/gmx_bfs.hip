@@ -393,17 +393,6 @@ __global__ void bfs_queue_bitmap_kernel(const int32_t* __restrict__ q, int64_t n
     }
 }
 
-// queue of a level straight from dist[] (ballot-aggregated append)
-__global__ void bfs_level_queue_kernel(const int32_t* __restrict__ dist, int64_t V, int32_t level,
-                                       int32_t* __restrict__ q, unsigned long long* __restrict__ qcount) {
-    int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    const int64_t vend = (V + 63) / 64 * 64;
-    for (; v < vend; v += stride) {
-        wave_append(v < V && dist[v] == level, (int32_t) v, q, qcount, threadIdx.x & 63);
-    }
-}
-
 // queue of the vertices whose bit is set (the frontier a bottom-up level left behind): 8 bytes per 64 vertices to
 // read instead of their dist[] entries.  A block takes a contiguous run of words, counts its bits, claims its piece of
 // the queue with ONE atomic (atomics on one address retire at ~90 per microsecond: a claim per word cost 170 us at
@@ -507,7 +496,7 @@ struct gmx_bfs {
     int32_t level = 0;
     int64_t cur_count = 0, reached = 0, explored = 0;
     unsigned long long found_total = 0;   // bottom-up finds so far (the device counter runs on)
-    int64_t cur_edges = -1;           // out-edges of the current queue when the level that built it counted them, else -1
+    int64_t cur_edges = -1;           // out-edges of the current queue (every kernel that builds a queue counts them); -1: the frontier is a bitmap
     unsigned long long edges = 0;
     bool frontier_is_bitmap = false, frontier_bm_valid = false, pending_bottom_up = false;
     int32_t* cur_q = nullptr;
@@ -516,7 +505,12 @@ struct gmx_bfs {
     // host round trips, and with pageable memory each is a staged copy -- at RMAT-24 that was most of the time
     gmx_pinned<bfs_level_totals> h_tot;   // written by bfs_totals_kernel
     unsigned long long tot_tag = 0;
-    gmx_pinned<int64_t> h_mf;
+    // the branch gmx_bfs_step_begin took, for the GMX_BFS_DEBUG line of gmx_bfs_step_end: the level's form, where its frontier
+    // came from, how the bottom-up hints are coded, and the edges of a top-down level's queue
+    const char* form = "";
+    const char* origin = "";
+    const char* encoding = "";
+    int64_t form_edges = 0;
 };
 
 // The in-neighbour a bottom-up level tries first: of the first BFS_HINT_SCAN entries of the in-row the one with most
@@ -900,7 +894,7 @@ extern "C" int gmx_bfs_create(gmx_graph_t* g, int rank, int nranks, gmx_bfs_t** 
     if ((st = b->dist.alloc(V1)) || (st = b->q0.alloc(V1)) || (st = b->q1.alloc(V1)) || (st = gmx_frontier_scan_alloc(&b->fs, V1, 0)) ||
         (st = b->ctr.alloc(1)) || (st = b->qcount.alloc(1)) ||
         (st = b->bm[0].alloc((size_t) b->words)) || (st = b->bm[1].alloc((size_t) b->words)) || (st = b->cand.alloc((size_t) b->words)) ||
-        (st = b->hub_bits.alloc(BFS_HUBS / 64)) || (st = b->h_tot.alloc()) || (st = b->h_mf.alloc())) {
+        (st = b->hub_bits.alloc(BFS_HUBS / 64)) || (st = b->h_tot.alloc())) {
         delete b;
         return st;
     }
@@ -959,13 +953,6 @@ extern "C" int gmx_bfs_start(gmx_bfs_t* b, gmx_node_t root) {
     return GMX_OK;
 }
 
-// frontier out-degrees -> off[], returns their sum
-static int bfs_frontier_edges(gmx_bfs* b, int64_t* m_f) {
-    GMX_CHECK(gmx_frontier_offsets(b->g->begin.p, b->cur_q, b->cur_count, &b->fs, b->h_mf.p, false));
-    *m_f = *b->h_mf.p;
-    return GMX_OK;
-}
-
 extern "C" int gmx_bfs_step_begin(gmx_bfs_t* b, int* needs_exchange) {
     GMX_REQUIRE(b && needs_exchange, "NULL argument");
     *needs_exchange = 0;
@@ -974,30 +961,30 @@ extern "C" int gmx_bfs_step_begin(gmx_bfs_t* b, int* needs_exchange) {
     gmx_graph* g = b->g;
     const int64_t V = b->V;
     int64_t m_f = 0;
-    bool bottom_up, have_off = false, cleared = false;
+    bool bottom_up, cleared = false;
+    b->form = b->origin = b->encoding = "";
     if (b->frontier_is_bitmap) bottom_up = b->cur_count > V / 24;
     else {
-        if (b->cur_edges >= 0) m_f = b->cur_edges;   // counted by the level that built the queue: no pass, no read-back
-        else {
-            GMX_CHECK(bfs_frontier_edges(b, &m_f));
-            have_off = true;
-        }
+        // counted by the level that built the queue (the root's by bfs_init_kernel): no pass, no read-back
+        GMX_REQUIRE(b->cur_edges >= 0, "bfs: the queue's out-edges were not counted");
+        m_f = b->cur_edges;
         bottom_up = g->has_reverse && (b->cur_count > V / 20 || m_f > (g->E - b->explored) / 14);
         b->explored += m_f;
     }
     if (bottom_up) {
         // (next_count / next_edges are top-down counters: a bottom-up level neither reads nor writes them, and the switch back
         // to top-down clears them where it needs them -- a memset here was a launch slot of ~7 us per level)
+        b->form = b->cand_valid ? "bottom-up/cand" : "bottom-up/dist";
+        b->origin = " kept";           // the bitmap the bottom-up level before this one found
         if (!b->frontier_bm_valid) {   // first bottom-up level after queue levels: frontier = {v : dist[v] == level}
-            if (!b->frontier_is_bitmap && b->first_bm_level == b->level) {
-                // ... which the level out of the root has written already
-            } else if (!b->frontier_is_bitmap) {   // ... which is the queue the last top-down level wrote
+            if (b->first_bm_level == b->level) {
+                b->origin = " prewritten";   // ... which the level out of the root has written already
+            } else {                   // ... which is the queue the last top-down level wrote
+                b->origin = " from-queue";
                 if (!b->bm_clean[b->fr]) GMX_HIP(hipMemsetAsync(b->bm[b->fr].p, 0, sizeof(unsigned long long) * (size_t) b->words, 0));
                 hipLaunchKernelGGL(bfs_queue_bitmap_kernel, dim3(grid_for(b->cur_count, BFS_THREADS, 256 * 16)), dim3(BFS_THREADS), 0, 0,
                                    (const int32_t*) b->cur_q, b->cur_count, (unsigned int*) b->bm[b->fr].p);
-            } else
-                hipLaunchKernelGGL(bfs_level_bitmap_kernel, dim3(grid_for(V, BFS_THREADS, 256 * 16)), dim3(BFS_THREADS), 0, 0,
-                                   (const int32_t*) b->dist.p, V, b->level, b->bm[b->fr].p);
+            }
         }
         b->bm_clean[0] = b->bm_clean[1] = false;   // the frontier was just written, the level writes the other one
         const int64_t v_lo = (int64_t) b->rank * b->slice_words * 64;
@@ -1015,6 +1002,7 @@ extern "C" int gmx_bfs_step_begin(gmx_bfs_t* b, int* needs_exchange) {
         // long: the first bottom-up level of a run over at least 2^25 vertices (RMAT-26: 450 -> 323 us; the later levels, with
         // a fifth of the vertices still looking, were slower with it).  Otherwise the same 16 KiB are probed in memory.
         const bool use_lds = hub_words > 0 && !b->cand_valid && v_hi - v_lo >= bfs_hub_min_v();
+        b->encoding = g->bfs_hint_plain ? " plain" : use_lds ? " hubs-lds" : hub_words > 0 ? " hubs-mem" : "";
         hipLaunchKernelGGL(bfs_bottomup_part_kernel, dim3(grid_for((v_hi - v_lo + 3) / 4, BFS_THREADS, use_lds ? 256 * 7 : 256 * 32)), dim3(BFS_THREADS), 0, 0,
                            g->r_begin.p, g->r_node_idx.p, v_lo, v_hi, V, (const uint32_t*) b->bm[b->fr].p,
                            (const int32_t*) b->dist.p, b->bm[1 - b->fr].p, b->nranks == 1 ? b->dist.p : nullptr, b->level + 1, b->ctr.p,
@@ -1025,31 +1013,26 @@ extern "C" int gmx_bfs_step_begin(gmx_bfs_t* b, int* needs_exchange) {
         *needs_exchange = b->nranks > 1 ? 1 : 0;
     } else {
         b->cand_valid = false;         // a top-down level visits vertices the candidate bitmap would still hold
-        if (b->frontier_is_bitmap) {   // back from bottom-up: rebuild the queue and its edge offsets
+        if (b->frontier_is_bitmap) {   // back from bottom-up: the frontier is the bitmap the last bottom-up level found; rebuild the queue
+            b->origin = " from-bitmap";
             GMX_HIP(hipMemsetAsync(b->qcount.p, 0, sizeof(unsigned long long), 0));
-            if (b->frontier_bm_valid) {   // the frontier is the bitmap the last bottom-up level found
-                GMX_HIP(hipMemsetAsync(&b->ctr.p->next_count, 0, 2 * sizeof(unsigned long long), 0));   // next_count, next_edges
-                hipLaunchKernelGGL(bfs_bitmap_queue_kernel, dim3(grid_for((V + 63) / 64, BFS_THREADS, 256 * 4)), dim3(BFS_THREADS), 0, 0,
-                                   (const unsigned long long*) b->bm[b->fr].p, (V + 63) / 64, b->cur_q, b->qcount.p,
-                                   (const int32_t*) g->begin.p, b->ctr.p);
-                const unsigned long long tag = ++b->tot_tag;
-                hipLaunchKernelGGL(bfs_totals_kernel, dim3(1), dim3(64), 0, 0, (const bfs_counters*) b->ctr.p, b->h_tot.p, tag);
-                GMX_HIP(hipGetLastError());
-                GMX_CHECK(bfs_wait_totals(b, tag));
-                m_f = (int64_t) b->h_tot.p->next_edges;   // the offsets follow below, without a read-back
-            } else {
-                hipLaunchKernelGGL(bfs_level_queue_kernel, dim3(grid_for(V, BFS_THREADS, 256 * 16)), dim3(BFS_THREADS), 0, 0,
-                                   (const int32_t*) b->dist.p, V, b->level, b->cur_q, b->qcount.p);
-                GMX_CHECK(bfs_frontier_edges(b, &m_f));
-                have_off = true;
-            }
+            GMX_HIP(hipMemsetAsync(&b->ctr.p->next_count, 0, 2 * sizeof(unsigned long long), 0));   // next_count, next_edges
+            hipLaunchKernelGGL(bfs_bitmap_queue_kernel, dim3(grid_for((V + 63) / 64, BFS_THREADS, 256 * 4)), dim3(BFS_THREADS), 0, 0,
+                               (const unsigned long long*) b->bm[b->fr].p, (V + 63) / 64, b->cur_q, b->qcount.p,
+                               (const int32_t*) g->begin.p, b->ctr.p);
+            const unsigned long long tag = ++b->tot_tag;
+            hipLaunchKernelGGL(bfs_totals_kernel, dim3(1), dim3(64), 0, 0, (const bfs_counters*) b->ctr.p, b->h_tot.p, tag);
+            GMX_HIP(hipGetLastError());
+            GMX_CHECK(bfs_wait_totals(b, tag));
+            m_f = (int64_t) b->h_tot.p->next_edges;   // the offsets follow below, without a read-back
             b->frontier_is_bitmap = false;
             b->explored += m_f;
         }
         b->frontier_bm_valid = false;
+        b->form_edges = m_f;
         // the level out of the root, on sorted rows only (its kernel drops a repeat by comparing with the slot before; a
         // repeat elsewhere in an unsorted row would enter the queue once per copy): other rows take the general levels below
-        if (b->level == 0 && b->cur_count == 1 && b->root >= 0 && !have_off && g->rows_sorted) {
+        if (b->level == 0 && b->cur_count == 1 && b->root >= 0 && g->rows_sorted) {
             // (the counters are clear: bfs_init_kernel)  A row this large is followed by a bottom-up level: write its bitmap too
             // (liberal: a wrong guess costs a memset of the bitmap later, a missed one a pass over the queue now)
             const bool with_bm = g->has_reverse && b->bm_clean[b->fr] && m_f >= 64 && m_f >= V / 1024;
@@ -1062,6 +1045,7 @@ extern "C" int gmx_bfs_step_begin(gmx_bfs_t* b, int* needs_exchange) {
                 b->bm_clean[b->fr] = false;
                 b->first_bm_level = 1;
             }
+            b->form = with_bm && nb1 > 0 ? "first+bitmap" : "first";
             int32_t* t = b->cur_q;
             b->cur_q = b->next_q;
             b->next_q = t;
@@ -1069,7 +1053,8 @@ extern "C" int gmx_bfs_step_begin(gmx_bfs_t* b, int* needs_exchange) {
             GMX_HIP(hipGetLastError());
             return GMX_OK;
         }
-        if (!have_off && b->cur_count <= (1 << 20) && m_f <= 2 * b->cur_count + 1024) {   // a sparse frontier: one vertex per lane
+        if (b->cur_count <= (1 << 20) && m_f <= 2 * b->cur_count + 1024) {   // a sparse frontier: one vertex per lane
+            b->form = "sparse";
             GMX_HIP(hipMemsetAsync(&b->ctr.p->next_count, 0, 2 * sizeof(unsigned long long), 0));
             hipLaunchKernelGGL(bfs_topdown_sparse_kernel, dim3(grid_for(b->cur_count, BFS_THREADS, 1 << 20)), dim3(BFS_THREADS), 0, 0,
                                (const int32_t*) g->begin.p, (const int32_t*) g->node_idx.p, (const int32_t*) b->cur_q, b->cur_count, b->level,
@@ -1081,14 +1066,15 @@ extern "C" int gmx_bfs_step_begin(gmx_bfs_t* b, int* needs_exchange) {
             GMX_HIP(hipGetLastError());
             return GMX_OK;
         }
-        if (!have_off) {   // merge-path offsets of the queue
-            if (b->cur_count <= BFS_SMALL_SCAN) {
-                hipLaunchKernelGGL(bfs_degree_scan_small_kernel, dim3(1), dim3(1024), 0, 0, g->begin.p, (const int32_t*) b->cur_q,
-                                   (int) b->cur_count, b->fs.off.p, b->ctr.p);
-                cleared = true;
-            } else {
-                GMX_CHECK(gmx_frontier_offsets(g->begin.p, b->cur_q, b->cur_count, &b->fs, nullptr, false));
-            }
+        // merge-path offsets of the queue
+        if (b->cur_count <= BFS_SMALL_SCAN) {
+            b->form = "tiles/small-scan";
+            hipLaunchKernelGGL(bfs_degree_scan_small_kernel, dim3(1), dim3(1024), 0, 0, g->begin.p, (const int32_t*) b->cur_q,
+                               (int) b->cur_count, b->fs.off.p, b->ctr.p);
+            cleared = true;
+        } else {
+            b->form = "tiles/scan";
+            GMX_CHECK(gmx_frontier_offsets(g->begin.p, b->cur_q, b->cur_count, &b->fs, nullptr, false));
         }
         if (!cleared) GMX_HIP(hipMemsetAsync(&b->ctr.p->next_count, 0, 2 * sizeof(unsigned long long), 0));
         const int64_t nb = frontier_tiles(b->cur_count, m_f);
@@ -1134,9 +1120,13 @@ extern "C" int gmx_bfs_step_end(gmx_bfs_t* b, int64_t* next_count) {
     struct { unsigned long long next_count, next_edges; } h = {b->h_tot.p->next_count, b->h_tot.p->next_edges};
     const unsigned long long edges = b->h_tot.p->edges, found = b->h_tot.p->found;
     // a top-down level leaves its queue tail in next_count, a bottom-up level its finds in the running total
-    if (getenv("GMX_BFS_DEBUG"))
-        fprintf(stderr, "gmx bfs: level %d %s: frontier %lld -> inspected %llu, next frontier %lld\n", b->level, b->cur_edges == -2 ? "top-down" : "bottom-up",
-                (long long) b->cur_count, edges - b->edges, (long long) (b->cur_edges == -2 ? h.next_count : found - b->found_total));
+    if (getenv("GMX_BFS_DEBUG")) {
+        char tail[64] = "";   // a top-down level also says how many edges its queue had (what the level before counted)
+        if (b->cur_edges == -2) snprintf(tail, sizeof(tail), ", frontier edges %lld", (long long) b->form_edges);
+        fprintf(stderr, "gmx bfs: level %d %s: frontier %lld -> inspected %llu, next frontier %lld, form %s%s%s%s\n", b->level,
+                b->cur_edges == -2 ? "top-down" : "bottom-up", (long long) b->cur_count, edges - b->edges,
+                (long long) (b->cur_edges == -2 ? h.next_count : found - b->found_total), b->form, b->origin, b->encoding, tail);
+    }
     b->cur_count = b->cur_edges == -2 ? (int64_t) h.next_count : (int64_t) (found - b->found_total);
     b->found_total = found;
     b->cur_edges = b->cur_edges == -2 ? (int64_t) h.next_edges : -1;
