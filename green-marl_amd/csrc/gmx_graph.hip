@@ -400,6 +400,7 @@ void gmx_warm_modules() {
     gmx_touch_wcc();
     gmx_touch_kcore();
     gmx_touch_msf();
+    gmx_touch_color();
 }
 
 static int check_sizes(int64_t V, int64_t E) {

@@ -55,7 +55,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -133,6 +133,7 @@ def lib():
         L.gmx_scc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_wcc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_kcore.argtypes = [vp, C.c_int, vp, vp, C.POINTER(i32), C.POINTER(Stats)]
+        L.gmx_coloring.argtypes = [vp, vp, vp, vp, C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_msf.argtypes = [vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_communities.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_potential_friends.argtypes = [vp, i32, i32, vp, vp, i64, C.POINTER(i64), C.POINTER(Stats)]
@@ -507,6 +508,26 @@ class Graph:
         if components:
             return sel[:self.E].astype(bool), int(ne.value), int(tw.value), comp[:self.V], int(nc.value), st.as_dict()
         return sel[:self.E].astype(bool), int(ne.value), int(tw.value), st.as_dict()
+
+    def coloring(self, prio=None, depth=False):
+        """Greedy (first-fit) vertex colouring in a fixed vertex order -- returns (color[int32], num_colors, stats), with
+        depth=True (color, depth[int32], num_colors, stats).  prio[V] int32: a larger priority comes first, ties go to the
+        lower id; None: largest degree (out-slots + in-slots) first.  color == 0 is the greedy maximal independent set of
+        the order; depth[v] is the round that coloured v under the schedule in gmx.h (GMX_COLOR_*).  Any row order; needs
+        the reverse CSR."""
+        p = None
+        if prio is not None:
+            p = _i32(prio)
+            if p.shape != (self.V,):
+                raise ValueError("prio must have one entry per vertex")
+        color = np.zeros(max(self.V, 1), np.int32)
+        dep = np.zeros(max(self.V, 1), np.int32) if depth else None
+        n, st = C.c_int32(0), Stats()
+        _ck(lib().gmx_coloring(self._h, p.ctypes.data if p is not None and self.V else None, color.ctypes.data, dep.ctypes.data if depth else None,
+                               C.byref(n), C.byref(st)))
+        if depth:
+            return color[:self.V], dep[:self.V], int(n.value), st.as_dict()
+        return color[:self.V], int(n.value), st.as_dict()
 
     def communities(self, max_rounds=1000):
         """communities(G, comm): label propagation under the canonical tie rule and schedule (gmx.h) -- returns

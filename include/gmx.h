@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge, gmx_v_cover's select and gmx_msf's weight and in_forest are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -489,6 +489,50 @@ int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* layer_host,
  *                   received, the tail launch and the finish, on stderr (tools/msf_prof.py; synchronises at every step). */
 int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_forest_host, int64_t* num_edges, int64_t* total_weight, int32_t* comp_host,
             int64_t* num_comps, gmx_stats_t* stats);
+
+/* Greedy vertex colouring (the reference has no such program): first fit in a fixed vertex order, which is unique, computed
+ * in parallel rounds by the Jones-Plassmann schedule; colour class 0 is the greedy (lexicographically first) maximal
+ * independent set of the same order.
+ * Graph: every stored forward slot u -> w with u != w makes u and w neighbours, in whichever direction it is stored; a
+ * repeated slot is harmless, self-loop slots are read and ignored, rows are read in any order.  The neighbourhood of a
+ * vertex is its out-row plus its in-row, so the entry needs the reverse CSR: GMX_ERR_STATE on a GMX_GRAPH_NO_REVERSE graph.
+ * A graph stored in one direction only gives the same bytes as its symmetrised form.  Nothing is cached on the graph.
+ * Order: u is earlier than w when (prio[u], -u) > (prio[w], -w): the larger priority first, ties to the lower id.
+ * prio_host[V], or NULL: prio[v] = outdeg(v) + indeg(v), all stored slots counted (repeats and self loops included) from
+ * the CSR offsets alone, as an unsigned 32-bit sum: largest degree first.  The priority is a key only; any int32 values
+ * are compared without overflow.  prio_host all zero: first fit in id order.
+ * color_host[V]: color[v] = the smallest colour >= 0 that no earlier neighbour of v holds -- what one thread produces when
+ * it takes the vertices in that order.  *num_colors = the largest colour + 1 (0 for V = 0).
+ * depth_host[V] (or NULL: nothing is kept or downloaded): the number of vertices on the longest chain of successively
+ * earlier neighbours that ends at v, minus 1; 0 when v has no earlier neighbour.  depth is defined on the graph and the
+ * order; under the schedule below it is the round that coloured v.  Both arrays are byte-identical from run to run, under
+ * every knob below and between upload forms.
+ * g == NULL or color_host == NULL (checked before g is touched): GMX_ERR_ARG before any device call.  prio_host,
+ * depth_host, num_colors and stats may be NULL.  V = 0: GMX_OK.  E = 0 or only self loops: every colour 0 in one round.
+ * Schedule (it fixes the statistics): round 0 colours every vertex without an earlier neighbour, round r+1 those whose
+ * last earlier neighbour was coloured in round r; rounds are separated by a kernel boundary or a workgroup barrier.  A
+ * ready vertex takes the smallest colour none of its neighbours holds (the later ones hold none yet), then lowers the
+ * pending count of every neighbour without a colour; the decrement that returns 1 queues that neighbour exactly once.
+ * stats: iterations = rounds = max(depth) + 1, vertices_reached = the size of colour class 0, edges_examined = 6 E (both
+ * rows of every vertex are read to count, to colour and to release; the extra window passes below are not counted),
+ * kernel_ms = device time from the first launch to the last, h2d_ms = the priorities, d2h_ms = the downloads.
+ * Read at every call, neither the result nor the statistics depend on them:
+ *   GMX_COLOR_TAIL       one workgroup runs the rounds while the queue holds at most this many entries + row slots; 0:
+ *                        never; default 1024,
+ *   GMX_COLOR_WAVE_MIN   rows (out-slots + in-slots) of at least this many slots are coloured by a wave with a bitmap in
+ *                        LDS, shorter ones by 16 lanes with a 64-bit mask; at most and by default 65,
+ *   GMX_COLOR_BLOCK_MIN  rows of at least this many slots are coloured by a workgroup; at most 8192 (the bits of a wave's
+ *                        LDS slice), default 256,
+ *   GMX_COLOR_WINDOW     bits of the workgroup's bitmap, a multiple of 64 in 64 .. 262144 (default: 32 KB of LDS); a row
+ *                        that may need a colour beyond it is walked again per window of colours, floor(color / window)
+ *                        extra passes,
+ *   GMX_COLOR_LOG        one line per call on stderr: `gmx color: V <V> E <E> user_prio <0|1> rounds <r> grid_rounds <g>
+ *                        tail_rounds <t> group <n> wave <n> block <n> passes <p> colors <c> class0 <n>`, with g + t = r =
+ *                        iterations, group + wave + block = V, passes = the extra window passes, colors = *num_colors
+ *                        and class0 = vertices_reached,
+ *   GMX_COLOR_PHASES     the device time of count, colour per regime, release and tail launches on stderr
+ *                        (tools/color_prof.py). */
+int gmx_coloring(gmx_graph_t* g, const int32_t* prio_host, int32_t* color_host, int32_t* depth_host, int32_t* num_colors, gmx_stats_t* stats);
 
 /* communities(G, comm) (apps/src/communities.gm:1-24; driver apps/output_cpp/src/communities_main.cc:19): label-propagation
  * community detection.  comm[x] = x; then every vertex x counts the labels of its out-neighbours, once per slot (a
