@@ -315,6 +315,7 @@ void gmx_touch_wcc();
 void gmx_touch_kcore();
 void gmx_touch_msf();
 void gmx_touch_color();
+void gmx_touch_close();
 void gmx_warm_modules();   // once per process: load every translation unit's code object (see gmx_touch_*)
 
 static inline int gmx_bits_for(int64_t v) {  // bits needed to represent values in [0, v)

@@ -55,7 +55,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -134,6 +134,7 @@ def lib():
         L.gmx_wcc.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_kcore.argtypes = [vp, C.c_int, vp, vp, C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_coloring.argtypes = [vp, vp, vp, vp, C.POINTER(i32), C.POINTER(Stats)]
+        L.gmx_closeness.argtypes = [vp, C.c_int, vp, i32, vp, vp, vp, vp, C.POINTER(Stats)]
         L.gmx_msf.argtypes = [vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_communities.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(Stats)]
         L.gmx_potential_friends.argtypes = [vp, i32, i32, vp, vp, i64, C.POINTER(i64), C.POINTER(Stats)]
@@ -529,6 +530,27 @@ class Graph:
             return color[:self.V], dep[:self.V], int(n.value), st.as_dict()
         return color[:self.V], int(n.value), st.as_dict()
 
+    CLOSE_MODES = {"out": 0, "in": 1, "both": 2}
+
+    def closeness(self, mode="out", sources=None):
+        """Distance centralities by hop count -- returns (far[int64], reach[int32], ecc[int32], harm[uint64], stats).  mode
+        "out": v's distances to the sources along out-edges (forward CSR only), "in": from the sources to v, "both": the
+        slots read as undirected edges (both need the reverse CSR).  sources None: every vertex; else a list of pivots, a
+        repeated one counting again.  Over the sources at distance 0 < D < infinity: reach = their number, far = sum of D,
+        ecc = max of D, harm = sum of floor(2^32 / D).  All four are exact integers whose bytes no knob changes (gmx.h:
+        GMX_CLOSE_*); closeness_of() and harmonic_of() derive the usual doubles."""
+        m = self.CLOSE_MODES[mode] if isinstance(mode, str) else int(mode)
+        src = None
+        if sources is not None:
+            src = _i32(sources).reshape(-1)
+        n = max(self.V, 1)
+        far, reach, ecc, harm = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint64)
+        keep = np.zeros(1, np.int32)   # (a list of no sources is still a list: a non-NULL pointer)
+        st = Stats()
+        _ck(lib().gmx_closeness(self._h, m, None if src is None else (src if len(src) else keep).ctypes.data, 0 if src is None else len(src),
+                                far.ctypes.data, reach.ctypes.data, ecc.ctypes.data, harm.ctypes.data, C.byref(st)))
+        return far[:self.V], reach[:self.V], ecc[:self.V], harm[:self.V], st.as_dict()
+
     def communities(self, max_rounds=1000):
         """communities(G, comm): label propagation under the canonical tie rule and schedule (gmx.h) -- returns
         (comm[int32], rounds, converged, stats).  comm holds vertex ids; converged is 1 when comm is a fixpoint."""
@@ -679,6 +701,21 @@ class Graph:
         st = Stats()
         _ck(lib().gmx_triangle_counting_directed_part(self._h, part, nparts, C.byref(t), C.byref(st)))
         return t.value, st.as_dict()
+
+
+def closeness_of(far, reach, wasserman_faust=False):
+    """Closeness from Graph.closeness()'s integers: reach / far (0 where nothing is reached); with wasserman_faust=True
+    scaled by reach / (V - 1), the form that compares vertices of different components."""
+    far, reach = np.asarray(far, np.float64), np.asarray(reach, np.float64)
+    c = np.divide(reach, far, out=np.zeros_like(far), where=far > 0)
+    if wasserman_faust and len(c) > 1:
+        c = c * reach / (len(c) - 1)
+    return c
+
+
+def harmonic_of(harm):
+    """Harmonic centrality from Graph.closeness()'s fixed point: harm / 2^32 (from below by less than reach * 2^-32)."""
+    return np.asarray(harm, np.uint64).astype(np.float64) / 4294967296.0
 
 
 def path_from_prev(prev_node, begin, end):

@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge, gmx_v_cover's select and gmx_msf's weight and in_forest are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -533,6 +533,57 @@ int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_forest_host,
  *   GMX_COLOR_PHASES     the device time of count, colour per regime, release and tail launches on stderr
  *                        (tools/color_prof.py). */
 int gmx_coloring(gmx_graph_t* g, const int32_t* prio_host, int32_t* color_host, int32_t* depth_host, int32_t* num_colors, gmx_stats_t* stats);
+
+/* Closeness, harmonic centrality and eccentricity (the reference has no such program): the hop distances between every
+ * vertex and a set of sources, folded per vertex into four exact integers.  With them come the diameter (max ecc), the
+ * radius (min ecc over vertices with reach > 0) and the Wiener index (sum of far).  mode names the direction: */
+#define GMX_CLOSE_OUT  0   /* d(v -> s): v's distances TO the sources along out-edges; pulls over forward rows; forward CSR only */
+#define GMX_CLOSE_IN   1   /* d(s -> v): distances FROM the sources to v; pulls over reverse rows; needs the reverse CSR        */
+#define GMX_CLOSE_BOTH 2   /* stored slots read as undirected edges; pulls over both rows; needs the reverse CSR               */
+/* Sources: sources == NULL means every vertex is a source (nsources is ignored).  Otherwise the sums run over the listed
+ * sources only (pivot sampling; what the estimate means is the caller's business); a source listed twice is two
+ * independent columns and counts twice.  A source outside [0, V) or nsources < 0: GMX_ERR_ARG.  nsources == 0 with a list:
+ * all-zero outputs, GMX_OK.
+ * Per vertex v, with D(v, s) the hop distance in the mode's direction, over the columns s with 0 < D(v, s) < infinity (a
+ * column whose source is v itself contributes nothing):
+ *   reach_host[v] = the number of such columns,
+ *   far_host[v]   = sum of D,
+ *   ecc_host[v]   = max of D, 0 when reach[v] == 0,
+ *   harm_host[v]  = sum of R(D) with R(l) = floor(2^32 / l) in 64-bit integer arithmetic: harm / 2^32 is the harmonic
+ *                   centrality from below, 0 <= exact - harm / 2^32 < reach * 2^-32.
+ * The fixed point is deliberate: all four outputs are integer sums or maxima, so they do not depend on any order.  THE
+ * BYTES OF ALL FOUR ARRAYS ARE IDENTICAL UNDER EVERY KNOB, SWEEP WIDTH AND ROW REGIME BELOW, FROM RUN TO RUN AND BETWEEN
+ * UPLOAD FORMS, AND EQUAL A ONE-THREAD BFS FROM EVERY SOURCE.  Closeness (reach / far), the Wasserman-Faust form and harm /
+ * 2^32 as doubles are derived on the host (gmx.py closeness_of / harmonic_of, generated/closeness.cc), never on the device.
+ * Any output pointer and stats may be NULL.  g == NULL or a mode outside 0 .. 2: GMX_ERR_ARG.  V = 0: GMX_OK.  IN or BOTH
+ * on a graph without its reverse CSR: GMX_ERR_STATE; OUT works on a GMX_GRAPH_NO_REVERSE graph.  Rows are read in any
+ * order; repeats and self loops are harmless.  Nothing is cached on the graph.
+ * Schedule: the sources are taken 64 * words at a time (a sweep); a sweep is a bit-parallel multi-source traversal with
+ * `words` 64-bit words per vertex in each of seen / front / next.  Level l >= 1 is one pass over all vertices: a vertex that
+ * misses no column whose front is not empty only clears its next words (saturated); the others OR the front words over
+ * their row -- by their own lane, or listed and by a wave for rows of at least GMX_CLOSE_LONG_MIN slots -- until every
+ * missing column is covered, and add the popcount of the new columns to their own four accumulators.  No atomic touches
+ * the state or a result after the seeding.  A sweep ends with the first level that finds nothing; the host reads the
+ * new-pair counts of GMX_CLOSE_BATCH levels in one copy (at most one read per level), and a level launched past the
+ * sweep's last finds every vertex saturated and changes nothing.  There is NO DEPTH CAP: levels are int32 and nothing
+ * is stored per level.  The cost with all sources is
+ * (V / (64 * words)) sweeps x depth levels, each a pass over the vertices: the entry is meant for graphs up to about 2^18
+ * vertices with all sources, or for pivot lists on large ones.
+ * stats: iterations = level passes launched (each sweep's final empty one included), vertices_reached = pairs = sum of
+ * reach, edges_examined = row slots read, kernel_ms = device time from the first launch to the last (events), h2d_ms =
+ * the source list, d2h_ms = the downloads.
+ * Read at every call; the outputs and pairs do not depend on them, the other statistics do:
+ *   GMX_CLOSE_WORDS     1, 2 or 4 words per vertex (64, 128 or 256 sources a sweep), halved while half as many words
+ *                       still hold all the sources; default 4,
+ *   GMX_CLOSE_BATCH     levels launched per host read, 1 .. 4; default 4; levels is a multiple of it,
+ *   GMX_CLOSE_LONG_MIN  rows of at least this many slots (BOTH: forward + reverse) are walked by a wave; 1: every row;
+ *                       default 128,
+ *   GMX_CLOSE_LOG       one line per call on stderr: `gmx close: V <n> E <n> mode <m> sources <n> words <B> sweeps <n> levels
+ *                       <n> lane <n> wave <n> saturated <n> slots <n> pairs <n>`, with sweeps = ceil(sources / (64 B)),
+ *                       lane + wave + saturated = V * levels, levels = iterations, slots = edges_examined and pairs =
+ *                       vertices_reached. */
+int gmx_closeness(gmx_graph_t* g, int mode, const gmx_node_t* sources, int32_t nsources, int64_t* far_host, int32_t* reach_host, int32_t* ecc_host,
+                  uint64_t* harm_host, gmx_stats_t* stats);
 
 /* communities(G, comm) (apps/src/communities.gm:1-24; driver apps/output_cpp/src/communities_main.cc:19): label-propagation
  * community detection.  comm[x] = x; then every vertex x counts the labels of its out-neighbours, once per slot (a
