@@ -38,13 +38,13 @@
 #define COMM_REV_BLOCK 2048        // reverse rows longer than this are marked by a workgroup of their own
 #define COMM_WAVE_SHARE 8          // a wave's table holds LDS_SLOTS / COMM_WAVE_SHARE slots
 
-enum { K_SHORT, K_WAVE, K_BLOCK, K_OVF, K_PEND, K_BIG, K_NCTR };   // list lengths of the running half-round
+enum { K_SHORT, K_WAVE, K_BLOCK, K_OVF, K_PEND, K_BIG, K_SPLIT, K_NCTR };   // list lengths of the running half-round, and its class splits
 
 struct comm_rec {   // totals of one round
     unsigned int changes;
     unsigned int evals[3];       // rows evaluated by regime
     unsigned int overflowed;     // rows whose table filled
-    unsigned int pad;
+    unsigned int splits;         // levels of a label class given up because a part filled (comm_overflow_kernel)
     unsigned long long slots;
 };
 
@@ -483,6 +483,7 @@ __global__ void __launch_bounds__(COMM_THREADS) comm_overflow_kernel(comm_arrays
                     ownc = to;
                     break;
                 }
+                if (threadIdx.x == 0) atomicAdd(&a.ctr[K_SPLIT], 1u);
             }
             comm_block_reduce(best, ownc, s_best, s_own);
             if (threadIdx.x == 0) {
@@ -576,6 +577,7 @@ __global__ void comm_close_kernel(comm_arrays a, comm_rec* rec) {
         rec->changes += a.ctr[K_PEND];
         for (int c = 0; c < 3; c++) rec->evals[c] += a.ctr[c];
         rec->overflowed += a.ctr[K_OVF];
+        rec->splits += a.ctr[K_SPLIT];
         for (int c = 0; c < K_NCTR; c++) a.ctr[c] = 0u;
     }
 }
@@ -707,8 +709,8 @@ extern "C" int gmx_communities(gmx_graph_t* g, int32_t max_rounds, gmx_node_t* c
         if (round_log) {
             float ms = 0;
             GMX_HIP(hipEventElapsedTime(&ms, ev[4], ev[1]));
-            fprintf(stderr, "gmx communities round %d: evals %u short + %u wave + %u block (%u overflowed), slots %llu, changes %u, %.3f ms\n",
-                    (int) r, R.evals[0], R.evals[1], R.evals[2], R.overflowed, R.slots, R.changes, ms);
+            fprintf(stderr, "gmx communities round %d: evals %u short + %u wave + %u block (%u overflowed), slots %llu, changes %u, %.3f ms, splits %u\n",
+                    (int) r, R.evals[0], R.evals[1], R.evals[2], R.overflowed, R.slots, R.changes, ms, R.splits);
         }
         if (R.changes == 0) fixpoint = true;
         else rounds++;
