@@ -182,8 +182,8 @@ struct gmx_graph {
     // row u - (V - tc_hubs), bit w - (V - tc_hubs) (gmx_tc.hip)
     dbuf<uint32_t> tc_hub_bits;
     int64_t tc_hubs = 0;
-    // triangle_counting_directed: the two renumbered CSRs and the work items (gmx_tcd.hip), built on first use; the plan
-    // records the order it was built with
+    // triangle_counting_directed and clustering: the two renumbered CSRs and the work items (gmx_tcd.hip, gmx_tcd_plan.h; the
+    // hub matrix of gmx_lcc.hip), built on first use by either; the plan records the order it was built with
     tcd_plan* tcd_cache = nullptr;
     // v_cover: Deg0, the incident lists sorted by (Deg0 of the other end descending, uploaded slot ascending), their offsets
     // and the lowest incident slot per vertex (gmx_vcover.hip), built on first use
@@ -316,6 +316,7 @@ void gmx_touch_kcore();
 void gmx_touch_msf();
 void gmx_touch_color();
 void gmx_touch_close();
+void gmx_touch_lcc();
 void gmx_warm_modules();   // once per process: load every translation unit's code object (see gmx_touch_*)
 
 static inline int gmx_bits_for(int64_t v) {  // bits needed to represent values in [0, v)

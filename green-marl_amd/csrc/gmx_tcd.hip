@@ -9,7 +9,8 @@
 // loops take part literally (gmx.h).  `w > u` only picks every unordered pair of distinct VALUES of a row once, so T does
 // not depend on the vertex numbering, and the count runs on a renumbered copy.
 //
-// Plan (graph preprocessing: built on first use from the forward CSR alone, cached on the graph, outside kernel_ms):
+// Plan (graph preprocessing: built on first use from the forward CSR alone, cached on the graph, outside kernel_ms; the struct is
+// in gmx_tcd_plan.h because gmx_clustering, gmx_lcc.hip, shares the plan and keeps perm and |N(x)| with it):
 //   N      the undirected simple neighbourhood: keys (s,d) and (d,s) of every slot with s != d, sorted, repeats dropped;
 //   perm   ascending |N(x)| (stable: ties by id), or the identity with GMX_TCD_NO_ORDER=1;
 //   OUT'   the forward rows renumbered and sorted, repeats and self loops kept (E entries);
@@ -26,7 +27,7 @@
 // Multiplicity: walking UP'(u) (distinct values), every w found adds its RUN LENGTH in the tail; walking the tail, every
 // slot adds one.  Both give the number of tail slots whose value is in UP'(u).
 // Integer only: exact.  64-bit partials per lane, a shuffle reduction, one atomic add per wave.
-#include "gmx_internal.h"
+#include "gmx_tcd_plan.h"
 #include "gmx_tc_search.h"
 
 #include <rocprim/rocprim.hpp>
@@ -44,14 +45,6 @@
 #define TCD_CAP_MIN 64
 
 enum { TCD_TOTAL, TCD_NEXT, TCD_STAGED, TCD_MEMORY, TCD_SLOT_ALONE, TCD_SLOT_LIST, TCD_SLOT_TAIL, TCD_SLOT_EMPTY, TCD_NCTR };
-
-struct tcd_plan {
-    int64_t V = 0, E = 0, E_up = 0;
-    bool ordered = true;
-    double build_ms = 0;
-    dbuf<int32_t> out_begin, out_idx, up_begin, up_idx;
-    dbuf<int64_t> grp_off;   // [V + 1]
-};
 
 void gmx_tcd_plan_free(tcd_plan* p) { delete p; }
 
@@ -90,13 +83,18 @@ __global__ void tcd_extract_kernel(const uint64_t* __restrict__ keys, int64_t V,
     }
 }
 
-// ascending |N(x)|, as tc_degkey_kernel does it on a CSR
-__global__ void tcd_degkey_kernel(const int32_t* __restrict__ nbegin, int64_t V, uint32_t* __restrict__ key, int32_t* __restrict__ id) {
+// ascending |N(x)|, as tc_degkey_kernel does it on a CSR; deg[] keeps |N(x)| for gmx_clustering (key, id NULL: only that)
+__global__ void tcd_degkey_kernel(const int32_t* __restrict__ nbegin, int64_t V, uint32_t* __restrict__ key, int32_t* __restrict__ id,
+                                  int32_t* __restrict__ deg) {
     int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t) gridDim.x * blockDim.x;
     for (; i < V; i += stride) {
-        key[i] = (uint32_t) nbegin[i + 1] - (uint32_t) nbegin[i];   // (N has up to 2 E < 2^32 entries: the offsets may wrap, the difference does not)
-        id[i] = (int32_t) i;
+        const uint32_t d = (uint32_t) nbegin[i + 1] - (uint32_t) nbegin[i];   // (N has up to 2 E < 2^32 entries: the offsets may wrap, the difference does not)
+        deg[i] = (int32_t) d;   // (< V <= 2^31 - 1)
+        if (key) {
+            key[i] = d;
+            id[i] = (int32_t) i;
+        }
     }
 }
 
@@ -276,7 +274,7 @@ static int tcd_sort_keys(uint64_t* a, uint64_t* b, int64_t n, unsigned end_bit, 
     return GMX_OK;
 }
 
-static int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
+int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
     const int64_t V = g->V, E = g->E;
     hipStream_t s = 0;
     gmx_tick tick("tcd plan");
@@ -323,28 +321,33 @@ static int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
     }
     uint64_t* nkeys = oth;   // n keys of N; `cur` is free
     tick.mark("N");
-    // perm: ascending |N(x)|
-    wbuf<int32_t> perm;
-    if (ordered) {
+    // |N(x)| (kept on the plan: gmx_clustering's deg) and perm: ascending |N(x)| (kept: gmx_clustering maps its arrays back through it)
+    dbuf<int32_t>& perm = p->perm;
+    GMX_CHECK(p->deg.alloc((size_t) V));
+    {
         wbuf<int32_t> nbegin, id, order;
         wbuf<uint32_t> key, key2;
         wbuf<char> tmp;
         GMX_CHECK(nbegin.alloc((size_t) V + 1));
-        GMX_CHECK(id.alloc((size_t) V));
-        GMX_CHECK(order.alloc((size_t) V));
-        GMX_CHECK(key.alloc((size_t) V));
-        GMX_CHECK(key2.alloc((size_t) V));
-        GMX_CHECK(perm.alloc((size_t) V));
+        if (ordered) {
+            GMX_CHECK(id.alloc((size_t) V));
+            GMX_CHECK(order.alloc((size_t) V));
+            GMX_CHECK(key.alloc((size_t) V));
+            GMX_CHECK(key2.alloc((size_t) V));
+            GMX_CHECK(perm.alloc((size_t) V));
+        }
         hipLaunchKernelGGL(tcd_extract_kernel, dim3(tcd_grid(V + 1)), dim3(TCD_THREADS), 0, s, (const uint64_t*) nkeys, V, n, (int64_t) 0, nbegin.p,
                            (int32_t*) nullptr);
-        hipLaunchKernelGGL(tcd_degkey_kernel, dim3(tcd_grid(V)), dim3(TCD_THREADS), 0, s, (const int32_t*) nbegin.p, V, key.p, id.p);
+        hipLaunchKernelGGL(tcd_degkey_kernel, dim3(tcd_grid(V)), dim3(TCD_THREADS), 0, s, (const int32_t*) nbegin.p, V, key.p, id.p, p->deg.p);
         GMX_HIP(hipGetLastError());
-        size_t tb = 0;
-        GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, key.p, key2.p, id.p, order.p, (size_t) V, 0u, 32u, s));
-        GMX_CHECK(tmp.alloc(tb));
-        GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, key.p, key2.p, id.p, order.p, (size_t) V, 0u, 32u, s));
-        hipLaunchKernelGGL(tcd_invert_kernel, dim3(tcd_grid(V)), dim3(TCD_THREADS), 0, s, (const int32_t*) order.p, V, perm.p);
-        GMX_HIP(hipGetLastError());
+        if (ordered) {
+            size_t tb = 0;
+            GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, key.p, key2.p, id.p, order.p, (size_t) V, 0u, 32u, s));
+            GMX_CHECK(tmp.alloc(tb));
+            GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, key.p, key2.p, id.p, order.p, (size_t) V, 0u, 32u, s));
+            hipLaunchKernelGGL(tcd_invert_kernel, dim3(tcd_grid(V)), dim3(TCD_THREADS), 0, s, (const int32_t*) order.p, V, perm.p);
+            GMX_HIP(hipGetLastError());
+        }
     }
     tick.mark("perm");
     // UP': the half of N's keys that points upwards in the new numbering

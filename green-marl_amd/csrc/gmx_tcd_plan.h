@@ -1,0 +1,29 @@
+// gmx_tcd_plan.h -- the plan gmx_tcd.hip builds from the forward CSR, shared with gmx_lcc.hip (gmx_clustering).
+#ifndef GMX_TCD_PLAN_H_
+#define GMX_TCD_PLAN_H_
+
+#include "gmx_internal.h"
+
+struct tcd_plan {
+    int64_t V = 0, E = 0, E_up = 0;
+    bool ordered = true;
+    double build_ms = 0;
+    dbuf<int32_t> out_begin, out_idx, up_begin, up_idx;
+    dbuf<int64_t> grp_off;   // [V + 1]: the 64-slot groups of the OUT' rows
+    dbuf<int32_t> perm;      // [V] caller's id -> plan's id; empty: the identity (ordered == false)
+    dbuf<int32_t> deg;       // [V] |N(x)|, by the CALLER's id (where gmx_clustering's finishing kernel needs it)
+    // gmx_clustering's additions, built on its first call on the plan (gmx_lcc.hip) and freed with it
+    bool lcc_ready = false;
+    dbuf<int64_t> up_grp_off;   // [V + 1]: the 64-slot groups of the UP' rows
+    int64_t hubs = 0;           // the `hubs` highest plan ids, a multiple of 64 ...
+    dbuf<uint32_t> hub_bits;    // ... and UP' among them as a hubs x hubs bit matrix: row u - (V - hubs), bit w - (V - hubs)
+    double hub_ms = 0;
+};
+
+// builds the plan of g (gmx_tcd.hip); the caller owns *out (gmx_tcd_plan_free)
+int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out);
+// groups[v] = 64-slot groups of a row of begin[v + 1] - begin[v] slots: ceil((d - 1) / 64) from d = 2 on (defined in
+// gmx_tcd.hip and launched from gmx_lcc.hip too, through the defining unit's host stub like iota_kernel)
+__global__ void tcd_groups_kernel(const int32_t* __restrict__ begin, int64_t V, int64_t* __restrict__ groups);
+
+#endif

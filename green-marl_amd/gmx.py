@@ -55,7 +55,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -148,6 +148,7 @@ def lib():
         L.gmx_triangle_counting_part.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_triangle_counting_directed.argtypes = [vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_triangle_counting_directed_part.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_clustering.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_bfs_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
         L.gmx_bfs_free.argtypes = [vp]
         L.gmx_bfs_start.argtypes = [vp, i32]
@@ -701,6 +702,22 @@ class Graph:
         st = Stats()
         _ck(lib().gmx_triangle_counting_directed_part(self._h, part, nparts, C.byref(t), C.byref(st)))
         return t.value, st.as_dict()
+
+    def clustering(self, tri=True, deg=True, lcc=True):
+        """Per-vertex triangle counts and local clustering coefficients of the stored slots read as an undirected simple graph
+        -- returns (tri[int64], deg[int32], lcc[float64], triangles, wedges, stats); an array not asked for is None.  tri[v] is
+        the number of triangles through v, deg[v] its distinct neighbours, lcc[v] = 2 tri / (deg (deg - 1)) (0.0 below deg 2),
+        triangles = sum(tri) / 3 and wedges = sum(deg (deg - 1) / 2): transitivity is 3 * triangles / wedges, the average
+        clustering coefficient lcc.mean().  Forward CSR only, any row order (gmx.h: GMX_LCC_*)."""
+        n = max(self.V, 1)
+        t = np.zeros(n, np.int64) if tri else None
+        d = np.zeros(n, np.int32) if deg else None
+        c = np.zeros(n, np.float64) if lcc else None
+        T, W, st = C.c_int64(0), C.c_int64(0), Stats()
+        _ck(lib().gmx_clustering(self._h, t.ctypes.data if tri else None, d.ctypes.data if deg else None, c.ctypes.data if lcc else None,
+                                 C.byref(T), C.byref(W), C.byref(st)))
+        V = self.V
+        return (t[:V] if tri else None, d[:V] if deg else None, c[:V] if lcc else None, int(T.value), int(W.value), st.as_dict())
 
 
 def closeness_of(far, reach, wasserman_faust=False):

@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_clustering, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge, gmx_v_cover's select and gmx_msf's weight and in_forest are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -690,6 +690,47 @@ int gmx_triangle_counting_part(gmx_graph_t* g, int part, int nparts, int64_t* co
  * stats: iterations = 1, kernel_ms = the count kernel only (the plan is graph preprocessing); everything else zero. */
 int gmx_triangle_counting_directed(gmx_graph_t* g, int64_t* count, gmx_stats_t* stats);
 int gmx_triangle_counting_directed_part(gmx_graph_t* g, int part, int nparts, int64_t* count, gmx_stats_t* stats);
+
+/* Per-vertex triangle counts and local clustering coefficients (the reference has no such program).
+ * Graph read: the stored slots as an undirected simple graph, as gmx_wcc, gmx_msf and gmx_closeness in mode BOTH read them:
+ *     N(v) = { u != v : v -> u or u -> v is stored };  self loops and repeated slots change nothing.
+ *   deg_host[V]  (int32)  deg[v] = |N(v)|;
+ *   tri_host[V]  (int64)  tri[v] = #{ unordered {u, w} in N(v) : w in N(u) }, the triangles through v;
+ *   lcc_host[V]  (double) lcc[v] = (double) (2 * tri[v]) / (double) ((int64) deg[v] * (deg[v] - 1)) when deg[v] >= 2, else +0.0:
+ *                one IEEE division of two exact integers (numpy gives the same bytes from the same integers);
+ *   *triangles = (sum of tri) / 3, *wedges = sum of deg (deg - 1) / 2.  Transitivity is 3 * triangles / wedges, the average
+ *                clustering coefficient the mean of lcc; both are left to the caller.
+ * Each of the three arrays may be NULL: it is then neither written nor downloaded.  wedges and stats may be NULL.  The arrays
+ * are indexed by the caller's vertex ids.  Integers only on the device: everything is exact and byte-identical from run to run
+ * and under every knob below.
+ * triangles == NULL (checked before g is touched) or g == NULL: GMX_ERR_ARG before any device call.  V = 0: GMX_OK, nothing is
+ * written.  E = 0 or self loops only: GMX_OK, zero arrays, *triangles = *wedges = 0.  Rows are read in any order, with repeats,
+ * and only the forward CSR is read: a GMX_GRAPH_NO_REVERSE graph works and there is no GMX_ERR_STATE.
+ * Plan: gmx_triangle_counting_directed's, cached on the graph and shared with it (whichever of the two is called first builds
+ * it; GMX_LCC_NO_ORDER and GMX_TCD_NO_ORDER each rebuild a cached plan of the other order).  The first gmx_clustering call adds
+ * the work items of the upper lists and the adjacency among the H highest plan ids as an H x H bit matrix (H = 65536, or
+ * 131072 above 2^24 vertices, at most V, rounded down to a multiple of 64; rebuilt when H changes).  When the plan, the matrix
+ * or the call's per-vertex scratch cannot be allocated: GMX_ERR_NOMEM, and the message gives the byte count.
+ * On a symmetric graph without self loops and repeated slots *triangles = gmx_triangle_counting and
+ * 3 * *triangles = gmx_triangle_counting_directed.
+ * Knobs, read from the environment at every call; the results do not depend on them:
+ *   GMX_LCC_NO_ORDER=1   the plan keeps the graph's numbering; no hub matrix then (the highest ids are no hubs);
+ *   GMX_LCC_HUBS         H (0: no hubs);
+ *   GMX_LCC_CAP          (1024) upper-list entries a wave stages in LDS, clamped to [64, 1024]; longer ones are searched in memory;
+ *   GMX_LCC_ALONE        (4) a lane walks a side of up to this many entries by itself;
+ *   GMX_LCC_RATIO        (4) a wave streams the upper list of u while it is at most this many times the tail;
+ *   GMX_LCC_HUB_TAIL     (4) against a hub u the tail is probed while it is at most this many times the upper list of u;
+ *   GMX_LCC_PLAIN=1      the credits of the third corner as one global atomic per match instead of the packed LDS counters
+ *                        (the form the counters are measured against, tools/lcc_prof.py);
+ *   GMX_LCC_LOG=1        one line on stderr per call: `gmx clustering: plan V <V> E <E> up <|UP'|> order <degree|identity>
+ *                        built <0|1> build_ms <ms> hubs <H> hub_ms <ms>; cap <c> alone <a> ratio <r> hub_tail <t> w <lds|global>;
+ *                        items <staged> staged + <memory> memory; slots <alone> alone + <list> list + <tail> tail + <hub> hub +
+ *                        <empty> empty; credits <lds> lds + <global> global`: work items by where their list is searched, slots
+ *                        by regime (alone: walked by one lane, bit probes included; hub: bit probes by the wave), third-corner
+ *                        credits by route (lds + global = *triangles).
+ * stats: iterations = 1, kernel_ms = the count kernel and the finishing kernel (the plan is graph preprocessing),
+ * edges_examined = |UP'| (the undirected edges), vertices_reached = vertices with tri > 0, d2h_ms = the downloads. */
+int gmx_clustering(gmx_graph_t* g, int64_t* tri_host, int32_t* deg_host, double* lcc_host, int64_t* triangles, int64_t* wedges, gmx_stats_t* stats);
 
 /* The common-neighbour iterator, gm_common_neighbor_iter(G, s, d) (gm_common_neighbor_iter.cc:21-44): the slots of s's
  * row, in order and with their multiplicity, whose value occurs in d's row (Foreach(u: s.CommonNbrs(d)) <=>
