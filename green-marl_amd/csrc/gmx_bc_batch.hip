@@ -597,11 +597,11 @@ static int bcb_msbfs_trace(bool on, int64_t batch, int32_t levels, const unsigne
     return GMX_OK;
 }
 
-// the batches of width W; bc (device) is zeroed and then accumulates in seed order.  `started` is recorded once the work
+// the batches of width W; bc (device) is zeroed and then accumulates in seed order.  tm's kernel span begins once the work
 // buffers exist (no allocation after it)
 template <int W>
 static int bcb_run(gmx_graph* g, const gmx_node_t* seeds, const int32_t* seeds_dev, int32_t nseeds, int skip_root, const bcb_knobs& kn, float* bc,
-                   hipEvent_t started, int64_t* reached_out, int64_t* slots_out) {
+                   gmx_spans& tm, int64_t* reached_out, int64_t* slots_out) {
     const int64_t V = g->V;
     const int64_t pitch_words = ((V + 255) / 256) * 64;   // a staged column, in words of four vertices
     dbuf<float2> sd;
@@ -622,7 +622,7 @@ static int bcb_run(gmx_graph* g, const gmx_node_t* seeds, const int32_t* seeds_d
     GMX_CHECK(tally.alloc(1 + W));
     if (kn.msbfs) GMX_CHECK(ms_tally.alloc(MSB_TALLY));
     std::vector<unsigned int> h_counts(2 * BCB_MAX_PASSES);
-    GMX_HIP(hipEventRecord(started, 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     GMX_HIP(hipMemsetAsync(bc, 0, sizeof(float) * (size_t) V, 0));   // G.BC = 0
     const uint8_t* lvl8 = (const uint8_t*) lvl.p;
     const int vblocks = (int) ((V + 255) / 256);
@@ -742,21 +742,16 @@ static int bcb_call(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, int
     GMX_CHECK(bc.alloc((size_t) V));
     GMX_CHECK(seeds_dev.alloc((size_t) nseeds));
     if (nseeds) GMX_HIP(hipMemcpy(seeds_dev.p, seeds, sizeof(int32_t) * (size_t) nseeds, hipMemcpyHostToDevice));
-    gmx_event e0, e1;
-    GMX_CHECK(e0.create());
-    GMX_CHECK(e1.create());
+    gmx_spans tm;
     int64_t reached = 0, slots = 0;
-    if (W == 16) GMX_CHECK(bcb_run<16>(g, seeds, seeds_dev.p, nseeds, skip_root, kn, bc.p, e0, &reached, &slots));
-    else if (W == 32) GMX_CHECK(bcb_run<32>(g, seeds, seeds_dev.p, nseeds, skip_root, kn, bc.p, e0, &reached, &slots));
-    else GMX_CHECK(bcb_run<64>(g, seeds, seeds_dev.p, nseeds, skip_root, kn, bc.p, e0, &reached, &slots));
-    GMX_HIP(hipEventRecord(e1, 0));
-    GMX_HIP(hipEventSynchronize(e1));
+    if (W == 16) GMX_CHECK(bcb_run<16>(g, seeds, seeds_dev.p, nseeds, skip_root, kn, bc.p, tm, &reached, &slots));
+    else if (W == 32) GMX_CHECK(bcb_run<32>(g, seeds, seeds_dev.p, nseeds, skip_root, kn, bc.p, tm, &reached, &slots));
+    else GMX_CHECK(bcb_run<64>(g, seeds, seeds_dev.p, nseeds, skip_root, kn, bc.p, tm, &reached, &slots));
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.finish(stats));
     GMX_HIP(hipMemcpy(bc_host, bc.p, sizeof(float) * (size_t) V, hipMemcpyDeviceToHost));
     if (stats) {
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, e0, e1);
         stats->iterations = nseeds;
-        stats->kernel_ms = ms;
         stats->vertices_reached = reached;
         stats->edges_examined = slots;
     }

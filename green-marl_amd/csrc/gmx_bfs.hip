@@ -1156,10 +1156,9 @@ extern "C" int gmx_hop_dist(gmx_graph_t* g, gmx_node_t root, int32_t* dist_host,
     if (g->V == 0) return GMX_OK;
     if (!g->bfs_cache) GMX_CHECK(gmx_bfs_create(g, 0, 1, &g->bfs_cache));   // graph preprocessing, like the reverse CSR
     gmx_bfs_t* b = g->bfs_cache;
-    gmx_event ev[4];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
     int st = GMX_OK;
-    (void) hipEventRecord(ev[0], 0);
+    GMX_CHECK(tm.begin(tm.KERNEL));
     if ((st = gmx_bfs_start(b, root)) == GMX_OK) {
         int64_t next = 0;
         int need = 0;
@@ -1168,8 +1167,8 @@ extern "C" int gmx_hop_dist(gmx_graph_t* g, gmx_node_t root, int32_t* dist_host,
             if ((st = gmx_bfs_step_end(b, &next)) != GMX_OK) break;
         } while (next > 0);
     }
-    (void) hipEventRecord(ev[1], 0);
-    (void) hipEventSynchronize(ev[1]);
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.sync(tm.KERNEL));
     unsigned long long edges_reached = 0;
     if (st == GMX_OK && stats) {   // statistics only, outside the timed traversal
         if (hipMemset(b->qcount.p, 0, sizeof(unsigned long long)) == hipSuccess) {
@@ -1178,18 +1177,11 @@ extern "C" int gmx_hop_dist(gmx_graph_t* g, gmx_node_t root, int32_t* dist_host,
         }
     }
     if (st == GMX_OK) {
-        (void) hipEventRecord(ev[2], 0);
+        GMX_CHECK(tm.begin(tm.D2H));
         st = gmx_bfs_download(b, dist_host, stats);
-        (void) hipEventRecord(ev[3], 0);
-        (void) hipEventSynchronize(ev[3]);
-        if (st == GMX_OK && stats) {
-            float ms = 0, cms = 0;
-            (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-            (void) hipEventElapsedTime(&cms, ev[2], ev[3]);
-            stats->kernel_ms = ms;
-            stats->d2h_ms = cms;
-            stats->edges_reached = (int64_t) edges_reached;
-        }
+        GMX_CHECK(tm.end(tm.D2H));
+        GMX_CHECK(tm.finish(st == GMX_OK ? stats : nullptr));
+        if (st == GMX_OK && stats) stats->edges_reached = (int64_t) edges_reached;
     }
     return st;
 }
@@ -1475,9 +1467,9 @@ __global__ void fill_f32_kernel(float* __restrict__ p, int64_t n, float v, int64
 }
 
 // comp_BC's seed loop on a device BC[]: BC[v] = BC[v] + delta_s[v] for every seed in order (gmx_bc below from BC = 0;
-// gmx_bc_batch, gmx_bc_batch.hip, for the batches it does not sweep itself).  `started` (optional) is recorded once the
+// gmx_bc_batch, gmx_bc_batch.hip, for the batches it does not sweep itself).  The kernel span of tm (optional) begins once the
 // work buffers exist, before the first kernel.
-int gmx_bc_seeds(gmx_graph* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, float* bc_dev, bool zero_bc, hipEvent_t started, int64_t* reached_out) {
+int gmx_bc_seeds(gmx_graph* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, float* bc_dev, bool zero_bc, gmx_spans* tm, int64_t* reached_out) {
     const int64_t V = g->V;
     if (!g->bfs_cache) GMX_CHECK(gmx_bfs_create(g, 0, 1, &g->bfs_cache));
     gmx_bfs* b = g->bfs_cache;
@@ -1489,7 +1481,7 @@ int gmx_bc_seeds(gmx_graph* g, const gmx_node_t* seeds, int32_t nseeds, int skip
     GMX_CHECK(sd.alloc((size_t) V));
     GMX_HIP(hipMemsetAsync(sd.p, 0, sizeof(float2) * (size_t) V, 0));   // (delta of a vertex no visit has written is never read; zero all the same)
     bfs_order ord;
-    if (started) GMX_HIP(hipEventRecord(started, 0));
+    if (tm) GMX_CHECK(tm->begin(tm->KERNEL));
     if (zero_bc) hipLaunchKernelGGL(fill_f32_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, bc_dev, V, 0.0f, (int64_t) -1, 0.0f);   // G.BC = 0
     int64_t reached = 0;
     for (int32_t si = 0; si < nseeds; si++) {   // For (s: Seeds.Items): sequential, as emitted
@@ -1514,19 +1506,14 @@ extern "C" int gmx_bc(gmx_graph_t* g, const gmx_node_t* seeds, int32_t nseeds, i
     for (int32_t i = 0; i < nseeds; i++) GMX_REQUIRE(seeds[i] >= 0 && seeds[i] < V, "seed %d out of range", seeds[i]);
     dbuf<float> bc;
     GMX_CHECK(bc.alloc((size_t) V));
-    gmx_event e0, e1;
-    GMX_CHECK(e0.create());
-    GMX_CHECK(e1.create());
+    gmx_spans tm;
     int64_t reached = 0;
-    GMX_CHECK(gmx_bc_seeds(g, seeds, nseeds, skip_root, bc.p, true, e0, &reached));
-    GMX_HIP(hipEventRecord(e1, 0));
-    GMX_HIP(hipEventSynchronize(e1));
+    GMX_CHECK(gmx_bc_seeds(g, seeds, nseeds, skip_root, bc.p, true, &tm, &reached));
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.finish(stats));
     GMX_HIP(hipMemcpy(bc_host, bc.p, sizeof(float) * (size_t) V, hipMemcpyDeviceToHost));
     if (stats) {
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, e0, e1);
         stats->iterations = nseeds;
-        stats->kernel_ms = ms;
         stats->vertices_reached = reached;
     }
     return GMX_OK;

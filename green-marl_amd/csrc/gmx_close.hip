@@ -429,8 +429,7 @@ extern "C" int gmx_closeness(gmx_graph_t* g, int mode, const gmx_node_t* sources
     if (sources) GMX_CHECK(sources_dev.alloc((size_t) nsources));
     gmx_pinned<unsigned long long> h_word;
     GMX_CHECK(h_word.alloc(CL_CTL + 1));
-    gmx_event ev[4];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
 
     cl_call c;
     c.g = g;
@@ -449,9 +448,10 @@ extern "C" int gmx_closeness(gmx_graph_t* g, int mode, const gmx_node_t* sources
     c.h_word = &h_word;
     c.sweeps = c.levels = c.pairs = 0;
 
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.H2D));
     if (sources && nsources) GMX_HIP(hipMemcpyAsync(sources_dev.p, sources, sizeof(int32_t) * (size_t) nsources, hipMemcpyHostToDevice, 0));
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.H2D));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     GMX_HIP(hipMemsetAsync(ctl.p, 0, sizeof(unsigned long long) * (CL_CTL + 1), 0));
     GMX_HIP(hipMemsetAsync(far.p, 0, sizeof(int64_t) * (size_t) V, 0));
     GMX_HIP(hipMemsetAsync(reach.p, 0, sizeof(int32_t) * (size_t) V, 0));
@@ -467,22 +467,19 @@ extern "C" int gmx_closeness(gmx_graph_t* g, int mode, const gmx_node_t* sources
     if (B == 1) GMX_CHECK(cl_run_mode<1>(c));
     else if (B == 2) GMX_CHECK(cl_run_mode<2>(c));
     else GMX_CHECK(cl_run_mode<4>(c));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.begin(tm.D2H));
     if (far_host) GMX_HIP(hipMemcpyAsync(far_host, far.p, sizeof(int64_t) * (size_t) V, hipMemcpyDeviceToHost, 0));
     if (reach_host) GMX_HIP(hipMemcpyAsync(reach_host, reach.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost, 0));
     if (ecc_host) GMX_HIP(hipMemcpyAsync(ecc_host, ecc.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost, 0));
     if (harm_host) GMX_HIP(hipMemcpyAsync(harm_host, harm.p, sizeof(uint64_t) * (size_t) V, hipMemcpyDeviceToHost, 0));
     GMX_HIP(hipMemcpyAsync(h_word.p, ctl.p, sizeof(unsigned long long) * CL_CTL, hipMemcpyDeviceToHost, 0));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));   // (the downloads have landed)
     const unsigned long long* h = h_word.p;
-    float ms = 0;
     stats->iterations = (int32_t) (c.levels > INT32_MAX ? INT32_MAX : c.levels);
     stats->vertices_reached = c.pairs;
     stats->edges_examined = (int64_t) h[CL_SLOTS];
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) stats->h2d_ms = ms;
-    if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) stats->kernel_ms = ms;
-    if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) stats->d2h_ms = ms;
     if (log)
         fprintf(stderr, "gmx close: V %lld E %lld mode %d sources %lld words %d sweeps %lld levels %lld lane %llu wave %llu saturated %llu slots %llu pairs %lld\n",
                 (long long) V, (long long) g->E, mode, (long long) n, B, (long long) c.sweeps, (long long) c.levels, h[CL_LANE], h[CL_WAVE], h[CL_SAT], h[CL_SLOTS],

@@ -532,34 +532,23 @@ extern "C" int gmx_coloring(gmx_graph_t* g, const int32_t* prio_host, int32_t* c
     gmx_pinned<co_ctl> h_ctl;
     GMX_CHECK(h_ctl.alloc());
     const co_ctl* h = h_ctl.p;
-    gmx_event ev[6];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
     const int gv = grid_for(V);
     enum { PH_COUNT, PH_GROUP, PH_WAVE, PH_BLOCK, PH_RELEASE, PH_TAIL, PH_N };
-    float ph_ms[PH_N] = {0, 0, 0, 0, 0, 0};   // (GMX_COLOR_PHASES): device time between two events around every step, which
-    gmx_event pev[2];                         // synchronises: the profiler's mode only
-    if (phase_log)
-        for (gmx_event& e : pev) GMX_CHECK(e.create());
-    auto phase_begin = [&] {
-        if (phase_log) (void) hipEventRecord(pev[0], 0);
-    };
-    auto phase_end = [&](int ph) {
-        float t = 0;
-        if (phase_log && hipEventRecord(pev[1], 0) == hipSuccess && hipEventSynchronize(pev[1]) == hipSuccess &&
-            hipEventElapsedTime(&t, pev[0], pev[1]) == hipSuccess)
-            ph_ms[ph] += t;
-    };
+    float ph_ms[PH_N] = {0, 0, 0, 0, 0, 0};   // (GMX_COLOR_PHASES): device time around every step, which
+    gmx_phase_clock phase;                    // synchronises: the profiler's mode only
+    GMX_CHECK(phase.enable(phase_log));
     const size_t block_lds = (size_t) window / 8;
     const size_t tail_lds = std::max(block_lds, sizeof(unsigned int) * (CO_TAIL_THREADS >> 6) * CO_WAVE_WORDS);
 
     // ---- the priorities
-    GMX_HIP(hipEventRecord(ev[4], 0));
+    GMX_CHECK(tm.begin(tm.H2D));
     if (prio_host) GMX_HIP(hipMemcpy(prio.p, prio_host, sizeof(int32_t) * (size_t) V, hipMemcpyHostToDevice));
-    GMX_HIP(hipEventRecord(ev[5], 0));
+    GMX_CHECK(tm.end(tm.H2D));
 
     // ---- count
-    GMX_HIP(hipEventRecord(ev[0], 0));
-    phase_begin();
+    GMX_CHECK(tm.begin(tm.KERNEL));
+    phase.begin();
     GMX_HIP(hipMemsetAsync(ctl.p, 0, sizeof(co_ctl), 0));
     GMX_HIP(hipMemsetAsync(pend.p, 0, sizeof(int32_t) * (size_t) V, 0));
     GMX_HIP(hipMemsetAsync(color.p, 0xff, sizeof(int32_t) * (size_t) V, 0));
@@ -571,7 +560,7 @@ extern "C" int gmx_coloring(gmx_graph_t* g, const int32_t* prio_host, int32_t* c
     hipLaunchKernelGGL(color_seed_kernel, dim3(grid_for(V, BFS_ITEMS)), dim3(CO_THREADS), 0, 0, S);
     GMX_HIP(hipGetLastError());
     GMX_CHECK(gmx_read_back(h_ctl, (const co_ctl*) ctl.p));
-    phase_end(PH_COUNT);
+    phase.end(&ph_ms[PH_COUNT]);
 
     // ---- rounds: colour the segment [qs, qe) of every list, then release its rows
     int64_t qs = 0, qe = (int64_t) h->qtail, ws = 0, we = (int64_t) h->wtail, bs = 0, be = (int64_t) h->btail;
@@ -582,11 +571,11 @@ extern "C" int gmx_coloring(gmx_graph_t* g, const int32_t* prio_host, int32_t* c
         const int64_t n = qe - qs;
         const int64_t m[2] = {at_qe[0] - at_qs[0], at_qe[1] - at_qs[1]};
         if (tail_from > 0 && n + m[0] + m[1] <= tail_from) {
-            phase_begin();
+            phase.begin();
             hipLaunchKernelGGL(color_tail_kernel, dim3(1), dim3(CO_TAIL_THREADS), tail_lds, 0, S, round, qs, qe, ws, we, bs, be, m[0], m[1], tail_from);
             GMX_HIP(hipGetLastError());
             GMX_CHECK(gmx_read_back(h_ctl, (const co_ctl*) ctl.p));
-            phase_end(PH_TAIL);
+            phase.end(&ph_ms[PH_TAIL]);
             tail_rounds += h->t_rounds;
             round += (int32_t) h->t_rounds;
             qs = h->t_qs;
@@ -602,20 +591,20 @@ extern "C" int gmx_coloring(gmx_graph_t* g, const int32_t* prio_host, int32_t* c
             if (h->t_state == CO_DONE) break;
             continue;   // CO_HANDBACK: the round it stopped at is too large for one workgroup and runs on the grid
         }
-        phase_begin();
+        phase.begin();
         hipLaunchKernelGGL(color_group_kernel, dim3(grid_for(n, CO_THREADS / 16)), dim3(CO_THREADS), 0, 0, S, (const int32_t*) (q.p + qs), n);
-        phase_end(PH_GROUP);
+        phase.end(&ph_ms[PH_GROUP]);
         if (we > ws) {
-            phase_begin();
+            phase.begin();
             hipLaunchKernelGGL(color_wave_kernel, dim3(grid_for(we - ws, CO_THREADS / 64)), dim3(CO_THREADS), 0, 0, S, (const int32_t*) (lw.p + ws), we - ws);
-            phase_end(PH_WAVE);
+            phase.end(&ph_ms[PH_WAVE]);
         }
         if (be > bs) {
-            phase_begin();
+            phase.begin();
             hipLaunchKernelGGL(color_block_kernel, dim3(grid_for(be - bs, 1)), dim3(CO_BLOCK_THREADS), block_lds, 0, S, (const int32_t*) (lb.p + bs), be - bs);
-            phase_end(PH_BLOCK);
+            phase.end(&ph_ms[PH_BLOCK]);
         }
-        phase_begin();
+        phase.begin();
         if (n <= CO_SMALL && m[0] + m[1] > 0)
             hipLaunchKernelGGL(color_offsets_kernel, dim3(1), dim3(CO_THREADS), 0, 0, S, (const int32_t*) (q.p + qs), (int) n, fs[0].off.p, fs[1].off.p);
         for (int d = 0; d < 2; d++) {
@@ -626,7 +615,7 @@ extern "C" int gmx_coloring(gmx_graph_t* g, const int32_t* prio_host, int32_t* c
         }
         GMX_HIP(hipGetLastError());
         GMX_CHECK(gmx_read_back(h_ctl, (const co_ctl*) ctl.p));
-        phase_end(PH_RELEASE);
+        phase.end(&ph_ms[PH_RELEASE]);
         grid_rounds++;
         round++;
         qs = qe;
@@ -642,30 +631,23 @@ extern "C" int gmx_coloring(gmx_graph_t* g, const int32_t* prio_host, int32_t* c
     }
     hipLaunchKernelGGL(color_finish_kernel, dim3(gv), dim3(CO_THREADS), 0, 0, (const int32_t*) color.p, V, ctl.p);
     GMX_HIP(hipGetLastError());
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     GMX_CHECK(gmx_read_back(h_ctl, (const co_ctl*) ctl.p));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpy(color_host, color.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
     if (depth_host) GMX_HIP(hipMemcpy(depth_host, depth.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));
 
     if ((int64_t) h->qtail != V || h->left) {
         gmx_set_error("coloring: %lld of %lld vertices became ready, %lld have no colour", (long long) h->qtail, (long long) V, (long long) h->left);
         return GMX_ERR_HIP;
     }
-    float ms = 0, cms = 0, hms = 0;
-    GMX_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    GMX_HIP(hipEventElapsedTime(&cms, ev[2], ev[3]));
-    GMX_HIP(hipEventElapsedTime(&hms, ev[4], ev[5]));
     const int32_t colors = h->maxcolor + 1;
     if (num_colors) *num_colors = colors;
     stats->iterations = round;
     stats->vertices_reached = (int64_t) h->class0;
     stats->edges_examined = 6 * E;
-    stats->kernel_ms = ms;
-    stats->h2d_ms = hms;
-    stats->d2h_ms = cms;
     if (phase_log)
         fprintf(stderr, "gmx color phases: count %.3f ms, group %.3f ms, wave %.3f ms, block %.3f ms, release %.3f ms, tail %.3f ms\n", ph_ms[PH_COUNT],
                 ph_ms[PH_GROUP], ph_ms[PH_WAVE], ph_ms[PH_BLOCK], ph_ms[PH_RELEASE], ph_ms[PH_TAIL]);

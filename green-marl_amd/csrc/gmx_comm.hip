@@ -658,8 +658,9 @@ extern "C" int gmx_communities(gmx_graph_t* g, int32_t max_rounds, gmx_node_t* c
     A.V = V;
     gmx_pinned<comm_rec> h_rec;
     GMX_CHECK(h_rec.alloc());
-    gmx_event ev[5];   // start, end, download start / end, round
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
+    gmx_phase_clock round_clock;   // GMX_COMM_ROUNDS: a round's two half-rounds
+    GMX_CHECK(round_clock.enable(round_log));
 
     const int word_grid = comm_grid((nwords + COMM_THREADS / 64 - 1) / (COMM_THREADS / 64), 2048);
     const int compact_grid = comm_grid((nwords + COMM_COMPACT_THREADS / 64 - 1) / (COMM_COMPACT_THREADS / 64), 1024);
@@ -689,29 +690,26 @@ extern "C" int gmx_communities(gmx_graph_t* g, int32_t max_rounds, gmx_node_t* c
 
     GMX_HIP(hipMemsetAsync(ctr.p, 0, sizeof(unsigned int) * K_NCTR, 0));
     GMX_HIP(hipMemsetAsync(shard.p, 0, sizeof(unsigned long long) * COMM_SHARDS, 0));
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     hipLaunchKernelGGL(comm_init_kernel, dim3(word_grid), dim3(COMM_THREADS), 0, 0, A, 1);
     int32_t rounds = 0;
     int64_t evals = 0, slots = 0;
     bool fixpoint = false;   // known: a round changed nothing
     for (int32_t r = 0; r < max_rounds && !fixpoint; r++) {
-        if (round_log) GMX_HIP(hipEventRecord(ev[4], 0));
+        round_clock.begin();
         if (!worklist && r > 0) hipLaunchKernelGGL(comm_init_kernel, dim3(word_grid), dim3(COMM_THREADS), 0, 0, A, 0);
         GMX_HIP(hipMemsetAsync(rec.p, 0, sizeof(comm_rec), 0));
         const uint32_t salt = (uint32_t) r * 0x9E3779B9u;
         GMX_CHECK(half_round(salt, 0, true, rec.p));
         GMX_CHECK(half_round(salt, 1, true, rec.p));
-        if (round_log) GMX_HIP(hipEventRecord(ev[1], 0));
+        const float round_ms = round_clock.end();
         GMX_CHECK(read_rec());
         const comm_rec& R = *h_rec.p;
         evals += (int64_t) R.evals[0] + R.evals[1] + R.evals[2];
         slots += (int64_t) R.slots;
-        if (round_log) {
-            float ms = 0;
-            GMX_HIP(hipEventElapsedTime(&ms, ev[4], ev[1]));
+        if (round_log)
             fprintf(stderr, "gmx communities round %d: evals %u short + %u wave + %u block (%u overflowed), slots %llu, changes %u, %.3f ms, splits %u\n",
-                    (int) r, R.evals[0], R.evals[1], R.evals[2], R.overflowed, R.slots, R.changes, ms, R.splits);
-        }
+                    (int) r, R.evals[0], R.evals[1], R.evals[2], R.overflowed, R.slots, R.changes, round_ms, R.splits);
         if (R.changes == 0) fixpoint = true;
         else rounds++;
     }
@@ -722,19 +720,14 @@ extern "C" int gmx_communities(gmx_graph_t* g, int32_t max_rounds, gmx_node_t* c
         GMX_CHECK(read_rec());
         fixpoint = h_rec.p->changes == 0;
     }
-    GMX_HIP(hipEventRecord(ev[1], 0));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpy(comm_host, comm.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
-    float ms = 0, cms = 0;
-    GMX_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    GMX_HIP(hipEventElapsedTime(&cms, ev[2], ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));
     if (rounds_out) *rounds_out = rounds;
     if (converged_out) *converged_out = fixpoint ? 1 : 0;
     stats->iterations = rounds;
-    stats->kernel_ms = ms;
-    stats->d2h_ms = cms;
     stats->vertices_reached = evals;
     stats->edges_examined = slots;
     return GMX_OK;

@@ -137,19 +137,15 @@ extern "C" int gmx_copy_bandwidth(int64_t bytes, int iters, double* gbs) {
     GMX_CHECK(a.alloc((size_t) n));
     GMX_CHECK(b.alloc((size_t) n));
     GMX_HIP(hipMemset(a.p, 1, (size_t) n * 16));
-    gmx_event e0, e1;
-    GMX_CHECK(e0.create());
-    GMX_CHECK(e1.create());
+    gmx_spans tm;
+    gmx_stats_t t{};
     hipLaunchKernelGGL(copy_f32x4_kernel, dim3(256 * 8), dim3(256), 0, 0, (const gmx_f32x4*) a.p, b.p, n);   // warm-up
-    (void) hipEventRecord(e0, 0);
+    GMX_CHECK(tm.begin(tm.KERNEL));
     for (int i = 0; i < iters; i++)
         hipLaunchKernelGGL(copy_f32x4_kernel, dim3(256 * 8), dim3(256), 0, 0, (const gmx_f32x4*) a.p, b.p, n);
-    (void) hipEventRecord(e1, 0);
-    hipError_t e = hipEventSynchronize(e1);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    GMX_HIP(e);
-    *gbs = 2.0 * (double) n * 16.0 * iters / (ms * 1e-3) / 1e9;   // bytes read + bytes written
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.finish(&t));
+    *gbs = 2.0 * (double) n * 16.0 * iters / (t.kernel_ms * 1e-3) / 1e9;   // bytes read + bytes written
     return GMX_OK;
 }
 

@@ -69,7 +69,7 @@ struct dbuf {
     T* take() { T* q = p; p = nullptr; n = 0; return q; }
 };
 
-// A hipEvent / pinned host words that are released on every return path.
+// A hipEvent that is released on every return path.
 struct gmx_event {
     hipEvent_t e = nullptr;
     gmx_event() {}
@@ -80,6 +80,83 @@ struct gmx_event {
     int create() { GMX_HIP(hipEventCreate(&e)); return GMX_OK; }
     operator hipEvent_t() const { return e; }
 };
+
+// The timed spans of gmx_stats_t.  An entry point says where its upload, its kernels and its download begin and end;
+// finish() waits for the last end and fills h2d_ms / kernel_ms / d2h_ms.  A span's two events are created at its first
+// begin(); a span that is never begun costs nothing and its field keeps the zero of the entry's memset.  A span that is
+// begun again adds to its sum (the earlier pair is read first, which waits for its end).  Every failure, that of reading
+// a recorded pair's time included, is GMX_ERR_HIP with the error text of GMX_HIP.
+struct gmx_spans {
+    enum span { H2D, KERNEL, D2H };
+    gmx_event ev[3][2];
+    double ms[3] = {0, 0, 0};
+    bool pending[3] = {false, false, false};   // ended, not yet added to ms
+    hipEvent_t last = nullptr;                 // the latest end
+    int begin(span s, hipStream_t st = 0) {
+        if (!ev[s][0].e) {
+            GMX_CHECK(ev[s][0].create());
+            GMX_CHECK(ev[s][1].create());
+        }
+        GMX_CHECK(fold(s));
+        GMX_HIP(hipEventRecord(ev[s][0], st));
+        return GMX_OK;
+    }
+    int end(span s, hipStream_t st = 0) {
+        GMX_HIP(hipEventRecord(ev[s][1], st));
+        pending[s] = true;
+        last = ev[s][1];
+        return GMX_OK;
+    }
+    int sync(span s) {   // wait for the span's end
+        GMX_HIP(hipEventSynchronize(ev[s][1]));
+        return GMX_OK;
+    }
+    hipEvent_t begin_event(span s) const { return ev[s][0]; }
+    int fold(span s) {
+        if (!pending[s]) return GMX_OK;
+        float t = 0;
+        GMX_CHECK(sync(s));
+        GMX_HIP(hipEventElapsedTime(&t, ev[s][0], ev[s][1]));
+        ms[s] += t;
+        pending[s] = false;
+        return GMX_OK;
+    }
+    // waits for the last end whether or not anyone reads the times: the asynchronous downloads of a d2h span have landed
+    int finish(gmx_stats_t* stats) {
+        if (last) GMX_HIP(hipEventSynchronize(last));
+        if (!stats) return GMX_OK;
+        for (int s = 0; s < 3; s++) GMX_CHECK(fold((span) s));
+        if (ev[H2D][0].e) stats->h2d_ms = ms[H2D];
+        if (ev[KERNEL][0].e) stats->kernel_ms = ms[KERNEL];
+        if (ev[D2H][0].e) stats->d2h_ms = ms[D2H];
+        return GMX_OK;
+    }
+};
+
+// GMX_*_PHASES: the device time of one phase at a time, added to a slot the caller names.  It synchronises at every
+// end(), so it is the profiler's mode only: off, it creates no events and does nothing.  Failures are swallowed.
+struct gmx_phase_clock {
+    bool on = false;
+    gmx_event ev[2];
+    int enable(bool want) {
+        if (want)
+            for (gmx_event& e : ev) GMX_CHECK(e.create());
+        on = want;
+        return GMX_OK;
+    }
+    void begin() {
+        if (on) (void) hipEventRecord(ev[0], 0);
+    }
+    float end(float* slot = nullptr) {   // the device time since begin() (0 when off or on failure)
+        float t = 0;
+        if (on && hipEventRecord(ev[1], 0) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+            hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess && slot)
+            *slot += t;
+        return t;
+    }
+};
+
+// Pinned host words that are released on every return path.
 template <typename T>
 struct gmx_pinned {
     T* p = nullptr;
@@ -209,9 +286,9 @@ struct gmx_graph {
 // root's whole traversal on g's single-rank traversal object (created on first use, as gmx_hop_dist does): *dist = its
 // device dist[] (INT_MAX = unreached, valid until the next traversal on g), *edges = edge slots inspected (gmx_bfs.hip)
 int gmx_bfs_reach(gmx_graph* g, int32_t root, const int32_t** dist, int64_t* edges);
-// comp_BC's per-seed loop on a device BC[V] (zero_bc: G.BC = 0 first); *reached = vertices reached, summed over the seeds.
+// comp_BC's per-seed loop on a device BC[V] (zero_bc: G.BC = 0 first; tm: begins its kernel span, or NULL); *reached = vertices reached, summed over the seeds.
 // The caller has checked g, the reverse CSR and the seeds (gmx_bfs.hip; gmx_bc and gmx_bc_batch's per-seed batches)
-int gmx_bc_seeds(gmx_graph* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, float* bc_dev, bool zero_bc, hipEvent_t started, int64_t* reached);
+int gmx_bc_seeds(gmx_graph* g, const gmx_node_t* seeds, int32_t nseeds, int skip_root, float* bc_dev, bool zero_bc, gmx_spans* tm, int64_t* reached);
 
 // ---- graph construction helpers (gmx_graph.hip) ----
 // keys are (row << 32 | col).  Sorts keys in place (double buffer), then writes

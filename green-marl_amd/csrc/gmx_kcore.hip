@@ -376,26 +376,15 @@ extern "C" int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* 
     gmx_pinned<kc_ctl> h_ctl;
     GMX_CHECK(h_ctl.alloc());
     const kc_ctl* h = h_ctl.p;
-    gmx_event ev[5];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
     const int gv = grid_for(V);
-    float ph_ms[4] = {0, 0, 0, 0};   // degrees, scans, grid rounds, tail (GMX_KCORE_PHASES): device time between two events around
-    gmx_event pev[2];                // every step; each step ends in a read-back, so the second event costs no overlap
-    if (phase_log)
-        for (gmx_event& e : pev) GMX_CHECK(e.create());
-    auto phase_begin = [&] {
-        if (phase_log) (void) hipEventRecord(pev[0], 0);
-    };
-    auto phase_end = [&](int ph) {
-        float t = 0;
-        if (phase_log && hipEventRecord(pev[1], 0) == hipSuccess && hipEventSynchronize(pev[1]) == hipSuccess &&
-            hipEventElapsedTime(&t, pev[0], pev[1]) == hipSuccess)
-            ph_ms[ph] += t;
-    };
+    float ph_ms[4] = {0, 0, 0, 0};   // degrees, scans, grid rounds, tail (GMX_KCORE_PHASES): device time around every step;
+    gmx_phase_clock phase;           // each step ends in a read-back, so the clock's wait costs no overlap
+    GMX_CHECK(phase.enable(phase_log));
 
     // ---- degrees
-    GMX_HIP(hipEventRecord(ev[0], 0));
-    phase_begin();
+    GMX_CHECK(tm.begin(tm.KERNEL));
+    phase.begin();
     GMX_HIP(hipMemsetAsync(ctl.p, 0, sizeof(kc_ctl), 0));
     if (mode == GMX_KCORE_IN && !g->has_reverse) {
         GMX_HIP(hipMemsetAsync(deg.p, 0, sizeof(int32_t) * (size_t) V, 0));
@@ -414,7 +403,7 @@ extern "C" int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* 
     if (phase_log) GMX_HIP(hipMemcpyAsync(deg0.p, deg.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToDevice, 0));
     GMX_CHECK(gmx_read_back(h_ctl, (const kc_ctl*) ctl.p));
     GMX_REQUIRE(!h->overflow, "kcore: a vertex has more than INT32_MAX counted slots");
-    phase_end(0);
+    phase.end(&ph_ms[0]);
 
     // ---- levels and rounds
     int32_t* la = l0.p;   // the live list (identity: the vertices 0 .. V-1, nothing stored yet)
@@ -429,12 +418,12 @@ extern "C" int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* 
         if (boundary && nlist == 0) break;
         const int64_t m[2] = {at_qe[0] - at_qs[0], at_qe[1] - at_qs[1]};
         if (tail_from > 0 && (boundary ? nlist : m[0] + m[1]) <= tail_from) {
-            phase_begin();
+            phase.begin();
             hipLaunchKernelGGL(kcore_tail_kernel, dim3(1), dim3(KC_TAIL_THREADS), 0, 0, S, la, lb, identity ? 1 : 0, nlist, k, round, qs, qe, level_q0, m[0], m[1],
                                tail_from);
             GMX_HIP(hipGetLastError());
             GMX_CHECK(gmx_read_back(h_ctl, (const kc_ctl*) ctl.p));
-            phase_end(3);
+            phase.end(&ph_ms[3]);
             if (h->t_levels) identity = false;
             if (h->t_swapped) std::swap(la, lb);
             levels += h->t_levels;
@@ -454,7 +443,7 @@ extern "C" int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* 
             continue;   // KC_BOUNDARY / KC_MIDLEVEL: the step it stopped at is too large for one workgroup and runs on the grid
         }
         if (qs == qe) {   // a level starts: its k, then the scan
-            phase_begin();
+            phase.begin();
             GMX_HIP(hipMemsetAsync(&ctl.p->shard[0], 0xff, sizeof(ctl.p->shard), 0));
             GMX_HIP(hipMemsetAsync(&ctl.p->nkeep, 0, sizeof(kc_word), 0));
             hipLaunchKernelGGL(kcore_min_kernel, dim3(grid_for(nlist)), dim3(KC_THREADS), 0, 0,
@@ -465,14 +454,14 @@ extern "C" int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* 
             for (int i = 0; i < BFS_SHARDS; i++) mn = std::min(mn, h->shard[i].mindeg);
             if (mn == KC_NONE) {   // every entry was removed by the last rounds
                 nlist = 0;
-                phase_end(1);
+                phase.end(&ph_ms[1]);
                 break;
             }
             hipLaunchKernelGGL(kcore_scan_kernel, dim3(grid_for(nlist, BFS_ITEMS)), dim3(KC_THREADS), 0, 0, S,
                                identity ? (const int32_t*) nullptr : (const int32_t*) la, nlist, k, (int32_t) mn, round, lb);
             GMX_HIP(hipGetLastError());
             GMX_CHECK(gmx_read_back(h_ctl, (const kc_ctl*) ctl.p));
-            phase_end(1);
+            phase.end(&ph_ms[1]);
             levels++;
             scanned += nlist;
             k = (int32_t) mn;
@@ -483,7 +472,7 @@ extern "C" int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* 
             qe = (int64_t) h->qtail;
             for (int d = 0; d < 2; d++) at_qe[d] = (int64_t) h->slots[d];
         } else {   // a round
-            phase_begin();
+            phase.begin();
             const int64_t n = qe - qs;
             for (int d = 0; d < S.ndir; d++) {
                 if (m[d] == 0) continue;
@@ -494,7 +483,7 @@ extern "C" int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* 
             }
             GMX_HIP(hipGetLastError());
             GMX_CHECK(gmx_read_back(h_ctl, (const kc_ctl*) ctl.p));
-            phase_end(2);
+            phase.end(&ph_ms[2]);
             grid_rounds++;
             round++;
             qs = qe;
@@ -509,13 +498,13 @@ extern "C" int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* 
         hipLaunchKernelGGL(kcore_maxdec_kernel, dim3(gv), dim3(KC_THREADS), 0, 0, (const int32_t*) deg0.p, (const int32_t*) deg.p, V, ctl.p);
         GMX_HIP(hipGetLastError());
     }
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     GMX_CHECK(gmx_read_back(h_ctl, (const kc_ctl*) ctl.p));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpy(core_host, core.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
     if (layer_host) GMX_HIP(hipMemcpy(layer_host, layer.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));
 
     if ((int64_t) h->qtail != V) {
         gmx_set_error("kcore: %lld of %lld vertices were removed", (long long) h->qtail, (long long) V);
@@ -523,15 +512,10 @@ extern "C" int gmx_kcore(gmx_graph_t* g, int mode, int32_t* core_host, int32_t* 
     }
     walked += h->t_walked;
     const int64_t top = V - level_q0;   // the last level's removals: the vertices of the largest core
-    float ms = 0, cms = 0;
-    GMX_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    GMX_HIP(hipEventElapsedTime(&cms, ev[2], ev[3]));
     if (max_core) *max_core = k;
     stats->iterations = round;
     stats->vertices_reached = top;
     stats->edges_examined = walked;
-    stats->kernel_ms = ms;
-    stats->d2h_ms = cms;
     if (phase_log)
         fprintf(stderr, "gmx kcore phases: degrees %.3f ms, scans %.3f ms, grid %.3f ms, tail %.3f ms, max_decrements %u\n", ph_ms[0], ph_ms[1], ph_ms[2], ph_ms[3],
                 h->maxdec);

@@ -446,10 +446,8 @@ extern "C" int gmx_clustering(gmx_graph_t* g, int64_t* tri_host, int32_t* deg_ho
         return GMX_ERR_NOMEM;
     }
     GMX_HIP(hipMemset(ctr.p, 0, LCC_NCTR * sizeof(unsigned long long)));
-    gmx_event ev0, ev1;
-    GMX_CHECK(ev0.create());
-    GMX_CHECK(ev1.create());
-    GMX_HIP(hipEventRecord(ev0, 0));
+    gmx_spans tm;
+    GMX_CHECK(tm.begin(tm.KERNEL));
     GMX_HIP(hipMemsetAsync(tri.p, 0, (size_t) V * sizeof(unsigned long long), 0));
     const uint32_t* bits = p->hubs ? (const uint32_t*) p->hub_bits.p : nullptr;
     const int32_t hub_base = (int32_t) (V - p->hubs);
@@ -464,10 +462,8 @@ extern "C" int gmx_clustering(gmx_graph_t* g, int64_t* tri_host, int32_t* deg_ho
     hipLaunchKernelGGL(lcc_finish_kernel, dim3(lcc_grid(V)), dim3(LCC_THREADS), 0, 0, (const unsigned long long*) tri.p, (const int32_t*) p->perm.p,
                        (const int32_t*) p->deg.p, V, tri_out.p, deg_out.p, lcc_out.p, ctr.p);
     GMX_HIP(hipGetLastError());
-    GMX_HIP(hipEventRecord(ev1, 0));
-    GMX_HIP(hipEventSynchronize(ev1));
-    float ms = 0;
-    (void) hipEventElapsedTime(&ms, ev0, ev1);
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.finish(stats));
     const double t0 = gmx_tick::now();
     unsigned long long h[LCC_NCTR];
     GMX_HIP(hipMemcpy(h, ctr.p, sizeof(h), hipMemcpyDeviceToHost));
@@ -479,8 +475,7 @@ extern "C" int gmx_clustering(gmx_graph_t* g, int64_t* tri_host, int32_t* deg_ho
     if (wedges) *wedges = (int64_t) h[LCC_WEDGES];
     if (stats) {
         stats->iterations = 1;
-        stats->kernel_ms = ms;
-        stats->d2h_ms = cms;
+        stats->d2h_ms = cms;   // (the host's clock around the blocking downloads, not a span of tm)
         stats->edges_examined = p->E_up;
         stats->vertices_reached = (int64_t) h[LCC_NONZERO];
     }

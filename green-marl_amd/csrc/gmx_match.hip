@@ -373,8 +373,7 @@ extern "C" int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_l
     GMX_CHECK(ctr.alloc(1));
     GMX_CHECK(gmx_frontier_scan_alloc(&fs, (size_t) V, 0));
     GMX_CHECK(h_ctr.alloc(1));
-    gmx_event ev[6];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
 
     rbm_state S;
     S.begin = g->begin.p;
@@ -389,10 +388,10 @@ extern "C" int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_l
     S.V = V;
     rbm_counters* h = h_ctr.p;
 
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.H2D));
     GMX_HIP(hipMemcpyAsync(is_left.p, is_left_host, (size_t) V, hipMemcpyHostToDevice, 0));
-    GMX_HIP(hipEventRecord(ev[1], 0));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.end(tm.H2D));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     const double t_start = gmx_tick::now();
     GMX_HIP(hipMemsetAsync(ctr.p, 0, sizeof(rbm_counters), 0));
     GMX_HIP(hipMemsetAsync(match.p, 0xff, sizeof(int32_t) * (size_t) V, 0));
@@ -444,7 +443,7 @@ extern "C" int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_l
         m = (int64_t) h->mlive;
         int32_t* x = la; la = lb; lb = x;
     }
-    GMX_HIP(hipEventRecord(ev[3], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     const double t_end = gmx_tick::now();
     const rbm_totals tot = rbm_sum(*h);
     if (h->bad) {
@@ -453,20 +452,13 @@ extern "C" int gmx_random_bipartite_matching(gmx_graph_t* g, const uint8_t* is_l
                       (unsigned) (w >> 32), (unsigned) (w & 0xffffffffu));
         return GMX_ERR_ARG;
     }
-    GMX_HIP(hipEventRecord(ev[4], 0));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpyAsync(match_host, match.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost, 0));
-    GMX_HIP(hipEventRecord(ev[5], 0));
-    GMX_HIP(hipEventSynchronize(ev[5]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));   // (the download has landed)
     *count = (int32_t) tot.matched;
-    float hms = 0, kms = 0, dms = 0;
-    (void) hipEventElapsedTime(&hms, ev[0], ev[1]);
-    (void) hipEventElapsedTime(&kms, ev[2], ev[3]);
-    (void) hipEventElapsedTime(&dms, ev[4], ev[5]);
     if (stats) {
         stats->iterations = round + tail_rounds;
-        stats->h2d_ms = hms;
-        stats->kernel_ms = kms;
-        stats->d2h_ms = dms;
         stats->edges_examined = grid_slots + (int64_t) tot.tail_slots;
         stats->edges_reached = (int64_t) tot.proposals;
         stats->vertices_reached = (int64_t) tot.matched;

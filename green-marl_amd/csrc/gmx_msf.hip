@@ -462,23 +462,13 @@ extern "C" int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_f
     gmx_pinned<msf_ctl> h_ctl;
     GMX_CHECK(h_ctl.alloc());
     const msf_ctl* h = h_ctl.p;
-    gmx_event ev[6];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
-    gmx_event pev[2];
-    if (phase_log)
-        for (gmx_event& e : pev) GMX_CHECK(e.create());
-    auto phase_begin = [&] {
-        if (phase_log) (void) hipEventRecord(pev[0], 0);
-    };
-    auto phase_end = [&]() -> float {   // device time since phase_begin (synchronises: the profiler's mode only)
-        float t = 0;
-        if (phase_log && hipEventRecord(pev[1], 0) == hipSuccess && hipEventSynchronize(pev[1]) == hipSuccess) (void) hipEventElapsedTime(&t, pev[0], pev[1]);
-        return t;
-    };
+    gmx_spans tm;
+    gmx_phase_clock phase;   // GMX_MSF_PHASES (synchronises: the profiler's mode only)
+    GMX_CHECK(phase.enable(phase_log));
     const int gv = grid_for(V);
 
     // ---- the weights: uploaded by the caller's slots, brought into the order of the device's
-    GMX_HIP(hipEventRecord(ev[4], 0));
+    GMX_CHECK(tm.begin(tm.H2D));
     const int32_t* weight_dev = nullptr;
     if (weight_host) {
         GMX_HIP(hipMemcpy(weight.p, weight_host, sizeof(int32_t) * (size_t) E, hipMemcpyHostToDevice));
@@ -489,7 +479,7 @@ extern "C" int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_f
             weight_dev = weight_sorted.p;
         }
     }
-    GMX_HIP(hipEventRecord(ev[5], 0));
+    GMX_CHECK(tm.end(tm.H2D));
 
     msf_state S;
     S.begin = g->begin.p;
@@ -505,7 +495,7 @@ extern "C" int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_f
     S.ctl = ctl.p;
     S.V = V;
 
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     GMX_HIP(hipMemsetAsync(ctl.p, 0, sizeof(msf_ctl), 0));
     GMX_HIP(hipMemsetAsync(flag.p, 0, (size_t) V, 0));
     GMX_HIP(hipMemsetAsync(in_forest.p, 0, (size_t) E, 0));
@@ -525,11 +515,11 @@ extern "C" int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_f
     int64_t rounds = 0, grid_rounds = 0, tail_rounds = 0, slots = 0, count = 0;
     while (n > 0) {
         if (tail_from > 0 && m <= tail_from) {
-            phase_begin();
+            phase.begin();
             hipLaunchKernelGGL(msf_tail_kernel, dim3(1), dim3(MSF_TAIL_THREADS), 0, 0, S, la, lb, n, roots.p, to.p);
             GMX_HIP(hipGetLastError());
             GMX_CHECK(gmx_read_back(h_ctl, (const msf_ctl*) ctl.p));
-            const float t = phase_end();
+            const float t = phase.end();
             tail_rounds = (int64_t) h->t_merging;
             rounds += tail_rounds;
             slots += (int64_t) h->t_slots;
@@ -541,16 +531,16 @@ extern "C" int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_f
         }
         float pt[3] = {0, 0, 0};
         GMX_HIP(hipMemsetAsync(&ctl.p->listed, 0, 2 * sizeof(msf_word), 0));
-        phase_begin();
+        phase.begin();
         GMX_CHECK(gmx_frontier_offsets(g->begin.p, la, n, &fs, nullptr, false));
         hipLaunchKernelGGL(msf_find_kernel, dim3((unsigned) frontier_tiles(n, m)), dim3(MSF_THREADS), 0, 0, S, (const int32_t*) la, n, (const int64_t*) fs.off.p, m);
-        pt[0] = phase_end();
-        phase_begin();
+        pt[0] = phase.end();
+        phase.begin();
         hipLaunchKernelGGL(msf_hook_kernel, dim3(gv), dim3(MSF_THREADS), 0, 0, S);
-        pt[1] = phase_end();
-        phase_begin();
+        pt[1] = phase.end();
+        phase.begin();
         hipLaunchKernelGGL(msf_next_kernel, dim3(grid_for(V, BFS_ITEMS)), dim3(MSF_THREADS), 0, 0, S, 0, lb);
-        pt[2] = phase_end();
+        pt[2] = phase.end();
         if (phase_log) hipLaunchKernelGGL(msf_maxatom_kernel, dim3(gv), dim3(MSF_THREADS), 0, 0, atoms.p, V, ctl.p);
         GMX_HIP(hipGetLastError());
         GMX_CHECK(gmx_read_back(h_ctl, (const msf_ctl*) ctl.p));
@@ -583,7 +573,7 @@ extern "C" int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_f
         size_t scan_bytes = 0;
         GMX_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, cflag.p, rank.p, 0, (size_t) V, rocprim::plus<int32_t>(), 0));
         GMX_CHECK(scan_tmp.alloc(scan_bytes));
-        phase_begin();
+        phase.begin();
         hipLaunchKernelGGL(msf_compress_kernel, dim3(gv), dim3(MSF_THREADS), 0, 0, parent.p, V, minv.p, size.p);
         hipLaunchKernelGGL(msf_trees_kernel, dim3(gv), dim3(MSF_THREADS), 0, 0, (const int32_t*) parent.p, V, minv.p, size.p);
         hipLaunchKernelGGL(msf_flag_kernel, dim3(gv), dim3(MSF_THREADS), 0, 0, (const int32_t*) parent.p, (const int32_t*) minv.p, V, cflag.p);
@@ -591,24 +581,20 @@ extern "C" int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_f
         hipLaunchKernelGGL(msf_comp_kernel, dim3(gv), dim3(MSF_THREADS), 0, 0, (const int32_t*) parent.p, (const int32_t*) minv.p, (const int32_t*) rank.p,
                            (const int32_t*) cflag.p, (const int32_t*) size.p, V, cbuf.p, ctl.p);
         GMX_HIP(hipGetLastError());
-        const float t = phase_end();
+        const float t = phase.end();
         if (phase_log) fprintf(stderr, "gmx msf finish: components %.3f ms\n", t);
         comp = cbuf.p;
     }
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     GMX_CHECK(gmx_read_back(h_ctl, (const msf_ctl*) ctl.p));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpy(in_forest_host, in_forest.p, (size_t) E, hipMemcpyDeviceToHost));
     if (comp) GMX_HIP(hipMemcpy(comp_host, comp, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));
 
     long long total = 0;
     for (int i = 0; i < BFS_SHARDS; i++) total += h->shard[i].weight;
-    float ms = 0, cms = 0, hms = 0;
-    GMX_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    GMX_HIP(hipEventElapsedTime(&cms, ev[2], ev[3]));
-    GMX_HIP(hipEventElapsedTime(&hms, ev[4], ev[5]));
     if (num_edges) *num_edges = count;
     if (total_weight) *total_weight = total;
     if (num_comps) *num_comps = V - count;
@@ -619,9 +605,6 @@ extern "C" int gmx_msf(gmx_graph_t* g, const int32_t* weight_host, uint8_t* in_f
     stats->iterations = (int32_t) rounds;
     stats->vertices_reached = comp ? (int64_t) h->largest : 0;
     stats->edges_examined = slots;
-    stats->kernel_ms = ms;
-    stats->h2d_ms = hms;
-    stats->d2h_ms = cms;
     if (getenv("GMX_MSF_LOG"))
         fprintf(stderr, "gmx msf: V %lld E %lld reverse %d rounds %lld grid_rounds %lld tail_rounds %lld slots %lld forest_edges %lld weight %lld comps %lld\n",
                 (long long) V, (long long) E, g->has_reverse ? 1 : 0, (long long) rounds, (long long) grid_rounds, (long long) tail_rounds, (long long) slots,

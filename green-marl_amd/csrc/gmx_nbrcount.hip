@@ -352,10 +352,9 @@ extern "C" int gmx_avg_teen_cnt(gmx_graph_t* g, const int32_t* age_host, int32_t
     GMX_CHECK(age.alloc((size_t) V));
     GMX_CHECK(cnt.alloc((size_t) V));
     GMX_CHECK(acc.alloc(2));
-    gmx_event ev[2];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
     GMX_HIP(hipMemcpy(age.p, age_host, sizeof(int32_t) * (size_t) V, hipMemcpyHostToDevice));
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     GMX_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (size_t) V, 0));
     GMX_HIP(hipMemsetAsync(acc.p, 0, 2 * sizeof(unsigned long long), 0));
     // n.teen_cnt = Count(t: n.InNbrs)(t.age >= 10 && t.age < 20)
@@ -371,7 +370,7 @@ extern "C" int gmx_avg_teen_cnt(gmx_graph_t* g, const int32_t* age_host, int32_t
     // Avg(n: G.Nodes)(n.age > K){n.teen_cnt}: int32 sum, int64 count (gm_syntax_sugar2.cc:264-296)
     hipLaunchKernelGGL(filtered_sum_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, (const int32_t*) age.p, (const int32_t*) cnt.p,
                        (const int32_t*) nullptr, V, 0, K, acc.p);
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     unsigned long long h[2];
     GMX_HIP(hipMemcpy(h, acc.p, sizeof(h), hipMemcpyDeviceToHost));
     GMX_HIP(hipMemcpy(teen_cnt_host, cnt.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
@@ -379,13 +378,8 @@ extern "C" int gmx_avg_teen_cnt(gmx_graph_t* g, const int32_t* age_host, int32_t
     const int64_t n = (int64_t) h[1];
     const double a = (0 == n) ? ((float) (0.000000)) : (S / ((double) n));
     *avg = (float) a;
-    if (stats) {
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-        stats->iterations = 1;
-        stats->kernel_ms = ms;
-    }
-    return GMX_OK;
+    if (stats) stats->iterations = 1;
+    return tm.finish(stats);
 }
 
 extern "C" int gmx_conduct(gmx_graph_t* g, const int32_t* member_host, int32_t num, float* result, gmx_stats_t* stats) {
@@ -394,15 +388,14 @@ extern "C" int gmx_conduct(gmx_graph_t* g, const int32_t* member_host, int32_t n
     *result = 0;
     const int64_t V = g->V;
     unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
-    gmx_event ev[2];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
     if (V > 0) {
         dbuf<int32_t> member;
         dbuf<unsigned long long> acc;   // [0,1] Din + count, [2,3] Dout + count, [4] Cross
         GMX_CHECK(member.alloc((size_t) V));
         GMX_CHECK(acc.alloc(6));
         GMX_HIP(hipMemcpy(member.p, member_host, sizeof(int32_t) * (size_t) V, hipMemcpyHostToDevice));
-        GMX_HIP(hipEventRecord(ev[0], 0));
+        GMX_CHECK(tm.begin(tm.KERNEL));
         GMX_HIP(hipMemsetAsync(acc.p, 0, 6 * sizeof(unsigned long long), 0));
         hipLaunchKernelGGL(filtered_sum_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, (const int32_t*) member.p, (const int32_t*) nullptr,
                            (const int32_t*) g->begin.p, V, 1, num, acc.p);
@@ -415,20 +408,15 @@ extern "C" int gmx_conduct(gmx_graph_t* g, const int32_t* member_host, int32_t n
             GMX_CHECK(count_by_bitmap(g->begin.p, g->node_idx.p, V, g->E, mem_bm.p, mem_bm.p, 1, nullptr, acc.p + 4));
             GMX_HIP(hipDeviceSynchronize());
         }
-        GMX_HIP(hipEventRecord(ev[1], 0));
+        GMX_CHECK(tm.end(tm.KERNEL));
         GMX_HIP(hipMemcpy(h, acc.p, sizeof(h), hipMemcpyDeviceToHost));
     }
     const int32_t Din = (int32_t) (uint32_t) h[0], Dout = (int32_t) (uint32_t) h[2], Cross = (int32_t) (uint32_t) h[4];
     const float m = (float) ((Din < Dout) ? Din : Dout);
     if (m == 0) *result = (Cross == 0) ? ((float) (0.000000)) : FLT_MAX;
     else *result = Cross / m;
-    if (stats && V > 0) {
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-        stats->iterations = 1;
-        stats->kernel_ms = ms;
-    }
-    return GMX_OK;
+    if (stats && V > 0) stats->iterations = 1;
+    return tm.finish(stats);
 }
 
 // (see gmx_touch_bfs)

@@ -2433,45 +2433,30 @@ static int pagerank_entry(gmx_graph_t* g, double e, double d, int32_t max_iter, 
         for (int64_t i = 0; i < g->V; i++) rank_host[i] = (S) tmp[(size_t) i];
         return GMX_OK;
     }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    gmx_spans tm;
     double diff = 0.0;
     int32_t cnt = 0;
     if (st == GMX_OK) {
-        (void) hipEventCreate(&ev0);
-        (void) hipEventCreate(&ev1);
-        (void) hipEventRecord(ev0, 0);
+        GMX_CHECK(tm.begin(tm.KERNEL));
         // do { ... cnt++; } while ((diff > e) && (cnt < max));   pagerank.gm:9-19
         do {
             if ((st = gmx_pr_step(p, nullptr)) != GMX_OK) break;
             if ((st = gmx_pr_diff(p, nullptr, &diff)) != GMX_OK) break;
             cnt++;
         } while ((diff > e) && (cnt < max_iter));
-        (void) hipEventRecord(ev1, 0);
-        (void) hipEventSynchronize(ev1);
+        GMX_CHECK(tm.end(tm.KERNEL));
+        GMX_CHECK(tm.sync(tm.KERNEL));
     }
     if (st == GMX_OK) {
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, ev0, ev1);
-        hipEvent_t c0, c1;
-        (void) hipEventCreate(&c0);
-        (void) hipEventCreate(&c1);
-        (void) hipEventRecord(c0, 0);
+        GMX_CHECK(tm.begin(tm.D2H));
         st = gmx_pr_download(p, rank_host);
-        (void) hipEventRecord(c1, 0);
-        (void) hipEventSynchronize(c1);
-        float cms = 0;
-        (void) hipEventElapsedTime(&cms, c0, c1);
-        (void) hipEventDestroy(c0);
-        (void) hipEventDestroy(c1);
+        GMX_CHECK(tm.end(tm.D2H));
+        GMX_CHECK(tm.finish(stats));
         if (stats) {
             stats->iterations = cnt;
             stats->last_diff = diff;
-            stats->kernel_ms = ms;
-            stats->d2h_ms = cms;
         }
     }
-    if (ev0) (void) hipEventDestroy(ev0);
-    if (ev1) (void) hipEventDestroy(ev1);
     return st;
 }
 

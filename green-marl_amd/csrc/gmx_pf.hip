@@ -514,29 +514,19 @@ extern "C" int gmx_potential_friends(gmx_graph_t* g, gmx_node_t v_lo, gmx_node_t
     gmx_pinned<unsigned long long> h_shard;
     GMX_CHECK(h_ctr.alloc(P_NCTR));
     GMX_CHECK(h_shard.alloc(3 * PF_SHARDS));
-    gmx_event ev[4];   // kernels start / end, download start / end
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
-    double kernel_ms = 0, d2h_ms = 0;
-    auto lap = [&](int a0, double* into) -> int {   // synchronises
-        float ms = 0;
-        GMX_HIP(hipEventSynchronize(ev[a0 + 1]));
-        GMX_HIP(hipEventElapsedTime(&ms, ev[a0], ev[a0 + 1]));
-        *into += ms;
-        return GMX_OK;
-    };
+    gmx_spans tm;   // the sizing pass, then a kernel + download lap per batch: each adds to its span's sum
 
     // counts
     pf_regimes reg;
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     hipLaunchKernelGGL(pf_len_kernel, dim3(pf_grid((n + PF_WAVES - 1) / PF_WAVES, 4096)), dim3(PF_THREADS), 0, 0, A, n);
     GMX_HIP(hipGetLastError());
     GMX_CHECK(pf_evaluate(A, P, 0, n, 0, h_ctr.p, h_shard.p, &reg));
-    GMX_HIP(hipEventRecord(ev[1], 0));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpy(pf_begin_host + 1, cnt.p, sizeof(int64_t) * (size_t) n, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_CHECK(lap(0, &kernel_ms));
-    GMX_CHECK(lap(2, &d2h_ms));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));
     int64_t reached = 0;
     for (int64_t i = 0; i < n; i++) {
         reached += pf_begin_host[i + 1] > 0;
@@ -546,8 +536,6 @@ extern "C" int gmx_potential_friends(gmx_graph_t* g, gmx_node_t v_lo, gmx_node_t
     if (total_out) *total_out = total;
     stats->edges_examined = (int64_t) (reg.items[0] + reg.items[1] + reg.items[2]);
     stats->vertices_reached = reached;
-    stats->kernel_ms = kernel_ms;
-    stats->d2h_ms = d2h_ms;
     if (!pf_idx_host || total > cap || total == 0) return GMX_OK;
 
     // fill, batch by batch over consecutive vertices; a row above the budget is a batch of its own
@@ -571,22 +559,18 @@ extern "C" int gmx_potential_friends(gmx_graph_t* g, gmx_node_t v_lo, gmx_node_t
         const int64_t items = pf_begin_host[i1] - pf_begin_host[i0];
         if (items > 0) {
             A.out_base = pf_begin_host[i0];
-            GMX_HIP(hipEventRecord(ev[0], 0));
+            GMX_CHECK(tm.begin(tm.KERNEL));
             GMX_CHECK(pf_evaluate(A, P, i0, i1, 1, h_ctr.p, h_shard.p, &reg));
-            GMX_HIP(hipEventRecord(ev[1], 0));
-            GMX_HIP(hipEventRecord(ev[2], 0));
+            GMX_CHECK(tm.end(tm.KERNEL));
+            GMX_CHECK(tm.begin(tm.D2H));
             GMX_HIP(hipMemcpy(pf_idx_host + pf_begin_host[i0], out.p, sizeof(int32_t) * (size_t) items, hipMemcpyDeviceToHost));
-            GMX_HIP(hipEventRecord(ev[3], 0));
-            GMX_CHECK(lap(0, &kernel_ms));
-            GMX_CHECK(lap(2, &d2h_ms));
+            GMX_CHECK(tm.end(tm.D2H));
             batches++;
         }
         i0 = i1;
     }
     stats->iterations = batches;
-    stats->kernel_ms = kernel_ms;
-    stats->d2h_ms = d2h_ms;
-    return GMX_OK;
+    return tm.finish(stats);
 }
 
 void gmx_touch_pf() {

@@ -560,16 +560,13 @@ int gmx_pr_multi_run(gmx_pr_multi* m, double e, double d, int32_t max_iter, void
         GMX_HIP(hipSetDevice(m->dev[r]));
         GMX_CHECK(gmx_pr_reset(m->pr[r], d));
     }
-    gmx_event ev0, ev1;
-    GMX_HIP(hipSetDevice(m->dev[0]));
-    GMX_CHECK(ev0.create());
-    GMX_CHECK(ev1.create());
+    gmx_spans tm;   // its events live on device 0: every begin / end below runs with that device current
     int st = GMX_OK;
     do {
         if ((st = exchange(m))) break;   // the reset filled every rank's own range of the current replica only
         if (!m->verified && m->nranks > 1 && (st = verify_replicas(m))) break;
         GMX_HIP(hipSetDevice(m->dev[0]));
-        (void) hipEventRecord(ev0, m->stream[0]);
+        if ((st = tm.begin(tm.KERNEL, m->stream[0]))) break;
         if (m->packed && !m->pipelined && m->exchange == EX_PEER && m->nranks > 1 && env_int("GMX_PR_MULTI_THREADS", 1) != 0) {
             if ((st = threaded_loop(m, e, max_iter, &diff, &cnt))) break;
         } else do {
@@ -598,34 +595,18 @@ int gmx_pr_multi_run(gmx_pr_multi* m, double e, double d, int32_t max_iter, void
         }
         if (st) break;
         GMX_HIP(hipSetDevice(m->dev[0]));
-        (void) hipEventRecord(ev1, m->stream[0]);
-        (void) hipEventSynchronize(ev1);
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, ev0, ev1);
-        double t0 = 0;
-        {
-            hipEvent_t c0, c1;
-            (void) hipEventCreate(&c0);
-            (void) hipEventCreate(&c1);
-            (void) hipEventRecord(c0, 0);
-            for (int r = 0; r < m->nranks && st == GMX_OK; r++) {
-                if (hipSetDevice(m->dev[r]) != hipSuccess) { gmx_set_error("hipSetDevice failed"); st = GMX_ERR_HIP; break; }
-                st = gmx_pr_download(m->pr[r], rank_host);   // scatters the rows this rank owns
-            }
-            (void) hipSetDevice(m->dev[0]);
-            (void) hipEventRecord(c1, 0);
-            (void) hipEventSynchronize(c1);
-            float cms = 0;
-            (void) hipEventElapsedTime(&cms, c0, c1);
-            t0 = cms;
-            (void) hipEventDestroy(c0);
-            (void) hipEventDestroy(c1);
+        if ((st = tm.end(tm.KERNEL, m->stream[0])) || (st = tm.sync(tm.KERNEL)) || (st = tm.begin(tm.D2H))) break;
+        for (int r = 0; r < m->nranks && st == GMX_OK; r++) {
+            if (hipSetDevice(m->dev[r]) != hipSuccess) { gmx_set_error("hipSetDevice failed"); st = GMX_ERR_HIP; break; }
+            st = gmx_pr_download(m->pr[r], rank_host);   // scatters the rows this rank owns
         }
+        (void) hipSetDevice(m->dev[0]);
+        int st2 = tm.end(tm.D2H);
+        if (st2 == GMX_OK) st2 = tm.finish(stats);
+        if (st == GMX_OK) st = st2;
         if (stats) {
             stats->iterations = cnt;
             stats->last_diff = diff;
-            stats->kernel_ms = ms;
-            stats->d2h_ms = t0;
         }
     } while (0);
     (void) hipSetDevice(m->home);

@@ -406,9 +406,8 @@ static int rt_create(gmx_route* r, gmx_graph* g, const int32_t* weight_host) {
     GMX_CHECK(r->h_ctl.alloc(1));
     if (V == 0) return GMX_OK;   // no vertex to ask for: every query is refused
     GMX_CHECK(r->w_f.alloc(E));
-    gmx_event ev[2];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    gmx_spans tm;
+    GMX_CHECK(tm.begin(tm.H2D));
     GMX_HIP(hipMemsetAsync(r->ctl.p, 0, sizeof(rt_ctl), 0));
     if (E) {
         // the weights: copied in, checked on the device copy, brought into the order of the sorted rows when the upload sorted them
@@ -452,7 +451,7 @@ static int rt_create(gmx_route* r, gmx_graph* g, const int32_t* weight_host) {
             GMX_HIP(hipGetLastError());
         }
     }
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.H2D));
     for (int s = 0; s < 2; s++) {
         GMX_CHECK(r->label[s].alloc(V));
         GMX_CHECK(r->stamp[s].alloc(V));
@@ -463,10 +462,9 @@ static int rt_create(gmx_route* r, gmx_graph* g, const int32_t* weight_host) {
     GMX_CHECK(r->out_n.alloc(V));
     GMX_CHECK(r->out_e.alloc(V));
     GMX_CHECK(gmx_frontier_scan_alloc(&r->fs, V, 0));
-    GMX_HIP(hipEventSynchronize(ev[1]));
-    float ms = 0;
-    (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-    r->h2d_ms = ms;
+    gmx_stats_t up{};
+    GMX_CHECK(tm.finish(&up));
+    r->h2d_ms = up.h2d_ms;
     return GMX_OK;
 }
 
@@ -514,8 +512,7 @@ extern "C" int gmx_route_query(gmx_route_t* r, gmx_node_t src, gmx_node_t dst, i
                     (gmx_tick::now() - t_start) * 1e3);
         return GMX_OK;
     }
-    gmx_event ev[4];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
 
     rt_dev D;
     D.side[0] = rt_side{g->begin.p, g->node_idx.p, r->w_f.p, r->label[0].p, r->stamp[0].p};
@@ -524,7 +521,7 @@ extern "C" int gmx_route_query(gmx_route_t* r, gmx_node_t src, gmx_node_t dst, i
     D.V = V;
     const rt_ctl* h = r->h_ctl.p;
 
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     hipLaunchKernelGGL(rt_init_kernel, dim3(grid_for(V, RT_THREADS)), dim3(RT_THREADS), 0, 0, D, (int32_t) src, (int32_t) dst, r->pos.p, r->q[0][0].p, r->q[1][0].p);
     GMX_HIP(hipGetLastError());
     GMX_CHECK(gmx_read_back(r->h_ctl, r->ctl.p));
@@ -596,23 +593,18 @@ extern "C" int gmx_route_query(gmx_route_t* r, gmx_node_t src, gmx_node_t dst, i
         GMX_REQUIRE(h->bad == 0, "route: a predecessor chain did not end");
         nhops = (int64_t) h->hops;
     }
-    GMX_HIP(hipEventRecord(ev[1], 0));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.begin(tm.D2H));
     const int64_t ncopy = nhops < cap ? nhops : cap;
     if (ncopy > 0 && path_node) GMX_HIP(hipMemcpyAsync(path_node, r->out_n.p, sizeof(int32_t) * (size_t) ncopy, hipMemcpyDeviceToHost, 0));
     if (ncopy > 0 && path_edge) GMX_HIP(hipMemcpyAsync(path_edge, r->out_e.p, sizeof(int32_t) * (size_t) ncopy, hipMemcpyDeviceToHost, 0));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));   // (the path has landed)
     *found = hit ? 1 : 0;
     if (hit) *cost = (int64_t) (mu >> 32);
     *hops = nhops;
     if (stats) {
-        float kms = 0, dms = 0;
-        (void) hipEventElapsedTime(&kms, ev[0], ev[1]);
-        (void) hipEventElapsedTime(&dms, ev[2], ev[3]);
         stats->iterations = grid_rounds[0] + grid_rounds[1] + tail_rounds[0] + tail_rounds[1];
-        stats->kernel_ms = kms;
-        stats->d2h_ms = dms;
         stats->edges_examined = slots[0] + slots[1];
         stats->vertices_reached = queued;
     }

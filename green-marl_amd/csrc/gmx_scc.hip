@@ -636,11 +636,10 @@ extern "C" int gmx_scc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
     R.a = scc_arrays{g->begin.p, g->node_idx.p, g->r_begin.p, g->r_node_idx.p, lab.p, cin.p, cout.p, col.p, mark.p, ctr.p, edges.p};
     GMX_CHECK(R.h_ctr.alloc(4));
     const scc_arrays& A = R.a;
-    gmx_event ev[4];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
     GMX_HIP(hipMemsetAsync(ctr.p, 0, sizeof(unsigned int) * C_NCTR, 0));
     GMX_HIP(hipMemsetAsync(edges.p, 0, sizeof(unsigned long long), 0));
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     // GMX_SCC_PHASES: an event at every phase boundary; the phases' shares of the timed span are added up at the end
     std::vector<std::pair<gmx_event, int>> phase_ev;
     auto phase_end = [&](int ph) {
@@ -810,7 +809,7 @@ extern "C" int gmx_scc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
     hipLaunchKernelGGL(scc_comp_kernel, dim3(scc_grid(V)), dim3(SCC_THREADS), 0, 0, (const int32_t*) lab.p, (const int32_t*) id, V, comp, ctr.p);
     GMX_HIP(hipGetLastError());
     phase_end(4);
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     int32_t last[2] = {0, 0};
     GMX_HIP(hipMemcpy(&last[0], id + V - 1, sizeof(int32_t), hipMemcpyDeviceToHost));
     GMX_HIP(hipMemcpy(&last[1], flag + V - 1, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -820,10 +819,10 @@ extern "C" int gmx_scc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
         gmx_set_error("scc: a vertex was left without a component");
         return GMX_ERR_STATE;
     }
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpy(comp_host, comp, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));
     // statistics outside the timed part: the largest component
     unsigned int largest = 1;   // (V > 0: a trimmed vertex at least)
     if (nrest > 0) {
@@ -840,17 +839,12 @@ extern "C" int gmx_scc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
     largest = std::max(largest, (unsigned int) giant);
     unsigned long long ed = 0;
     GMX_HIP(hipMemcpy(&ed, edges.p, sizeof(ed), hipMemcpyDeviceToHost));
-    float ms = 0, cms = 0;
-    GMX_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    GMX_HIP(hipEventElapsedTime(&cms, ev[2], ev[3]));
     *num_comps = (int64_t) last[0] + last[1];
     stats->iterations = rounds;
     stats->vertices_reached = largest;
     stats->edges_examined += (int64_t) ed;
-    stats->kernel_ms = ms;
-    stats->d2h_ms = cms;
     if (phase_log) {
-        hipEvent_t prev = ev[0];
+        hipEvent_t prev = tm.begin_event(tm.KERNEL);
         for (auto& e : phase_ev) {
             float t = 0;
             (void) hipEventElapsedTime(&t, prev, e.first);

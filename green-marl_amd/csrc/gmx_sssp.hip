@@ -111,13 +111,12 @@ extern "C" int gmx_sssp(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host
     relax_scratch S;
     GMX_CHECK(dist.alloc((size_t) V));
     GMX_CHECK(S.alloc(g));
-    gmx_event ev[4];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    gmx_spans tm;
+    GMX_CHECK(tm.begin(tm.H2D));
     GMX_CHECK(S.upload_len(g, len_host));
     GMX_CHECK(S.reorder_len(g));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.end(tm.H2D));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     hipLaunchKernelGGL(sssp_init_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, dist.p, S.stamp.p, V, root_ok ? root : -1);
     int64_t cur_count = 0, requeued = 0;
     unsigned long long edges = 0;
@@ -150,16 +149,11 @@ extern "C" int gmx_sssp(gmx_graph_t* g, gmx_node_t root, const int32_t* len_host
         next_q = t;
         round++;
     }
-    GMX_HIP(hipEventRecord(ev[1], 0));
-    GMX_HIP(hipEventSynchronize(ev[1]));
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.finish(stats));
     GMX_HIP(hipMemcpy(dist_host, dist.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
     if (stats) {
-        float ms = 0, hms = 0;
-        (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-        (void) hipEventElapsedTime(&hms, ev[2], ev[3]);
         stats->iterations = round;
-        stats->kernel_ms = ms;
-        stats->h2d_ms = hms;
         stats->edges_examined = (int64_t) edges;
         stats->vertices_reached = requeued + (root_ok ? 1 : 0);   // queue entries over all rounds (a vertex may re-enter)
     }
@@ -407,11 +401,10 @@ extern "C" int gmx_sssp_path(gmx_graph_t* g, gmx_node_t root, const int32_t* len
         GMX_CHECK(far0.alloc(far_cap));
         GMX_CHECK(far1.alloc(far_cap));
     }
-    gmx_event ev[6];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
     // the property: copied in, checked on the device copy (negative lengths are refused), brought into the order of the
     // sorted rows when the upload sorted them
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.begin(tm.H2D));
     unsigned long long h_chk[2] = {0, 0};
     GMX_CHECK(S.upload_len(g, len_host));
     if (E) {
@@ -422,7 +415,7 @@ extern "C" int gmx_sssp_path(gmx_graph_t* g, gmx_node_t root, const int32_t* len
         GMX_REQUIRE(h_chk[0] == 0, "len holds %llu negative value(s): gmx_sssp_path needs len >= 0", h_chk[0]);
     }
     GMX_CHECK(S.reorder_len(g));
-    GMX_HIP(hipEventRecord(ev[3], 0));
+    GMX_CHECK(tm.end(tm.H2D));
     // near / far: delta = 32 * mean length / mean out-degree (a queue round then holds about a wave's worth of edges per
     // vertex of the band), at least 1
     uint32_t delta = 1;
@@ -434,7 +427,7 @@ extern "C" int gmx_sssp_path(gmx_graph_t* g, gmx_node_t root, const int32_t* len
     }
     const uint32_t T_ALL = 0x80000000u;   // above every distance
     uint32_t T = nearfar ? delta : T_ALL;
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     hipLaunchKernelGGL(sp_init_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, key.p, S.stamp.p, V, root_ok ? root : -1);
     int64_t cur_count = 0, queued = 0, far_n = 0;
     unsigned long long edges = 0;
@@ -521,23 +514,16 @@ extern "C" int gmx_sssp_path(gmx_graph_t* g, gmx_node_t root, const int32_t* len
     hipLaunchKernelGGL(sp_finish_kernel, dim3(grid_for(V)), dim3(BFS_THREADS), 0, 0, (const unsigned long long*) key.p, (const int32_t*) g->begin.p,
                        (const int32_t*) g->e_idx2idx.p, V, out.p, out.p + V, out.p + 2 * V);
     GMX_HIP(hipGetLastError());
-    GMX_HIP(hipEventRecord(ev[1], 0));
-    GMX_HIP(hipEventSynchronize(ev[1]));
-    GMX_HIP(hipEventRecord(ev[4], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.sync(tm.KERNEL));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpy(dist_host, out.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
     GMX_HIP(hipMemcpy(prev_node_host, out.p + V, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
     if (prev_edge_host) GMX_HIP(hipMemcpy(prev_edge_host, out.p + 2 * V, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[5], 0));
-    GMX_HIP(hipEventSynchronize(ev[5]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));
     if (stats) {
-        float ms = 0, hms = 0, dms = 0;
-        (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-        (void) hipEventElapsedTime(&hms, ev[2], ev[3]);
-        (void) hipEventElapsedTime(&dms, ev[4], ev[5]);
         stats->iterations = rounds;
-        stats->kernel_ms = ms;
-        stats->h2d_ms = hms;
-        stats->d2h_ms = dms;
         stats->edges_examined = (int64_t) edges;
         stats->vertices_reached = queued;   // queue entries over all rounds (a vertex may re-enter), the root's included
     }

@@ -336,8 +336,7 @@ extern "C" int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end
         g->spf_cache = fresh;
     }
     spf_scratch& W = *g->spf_cache;
-    gmx_event ev[6];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
 
     spf_state S;
     S.begin = g->begin.p;
@@ -356,7 +355,7 @@ extern "C" int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end
     spf_counters* h = W.h_ctr.p;
 
     // the property: copied in, checked on the device copy, brought into the order of the sorted rows when the upload sorted them
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.H2D));
     GMX_HIP(hipMemsetAsync(W.ctr.p, 0, sizeof(spf_counters), 0));
     if (E) {
         GMX_HIP(hipMemcpyAsync(W.cost.p, cost_host, sizeof(double) * (size_t) E, hipMemcpyHostToDevice, 0));
@@ -374,9 +373,9 @@ extern "C" int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end
             S.cost = W.cost_sorted.p;
         }
     }
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.H2D));
 
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     const double t_start = gmx_tick::now();
     int32_t* la = W.q0.p;   // the queue of the next round
     int32_t* lb = W.q1.p;
@@ -429,24 +428,17 @@ extern "C" int gmx_sssp_path_f64(gmx_graph_t* g, gmx_node_t root, gmx_node_t end
         m = (int64_t) h->mnext;
         if (n == 0) rounds++;        // vertices dropped, none of them below the bound with a row: one more round, which offers nothing
     }
-    GMX_HIP(hipEventRecord(ev[3], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     const double t_end = gmx_tick::now();
 
-    GMX_HIP(hipEventRecord(ev[4], 0));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpyAsync(dist_host, W.dist.p, sizeof(double) * (size_t) V, hipMemcpyDeviceToHost, 0));
     GMX_HIP(hipMemcpyAsync(prev_node_host, W.prev_node.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost, 0));
     if (prev_edge_host) GMX_HIP(hipMemcpyAsync(prev_edge_host, W.prev_edge.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost, 0));
-    GMX_HIP(hipEventRecord(ev[5], 0));
-    GMX_HIP(hipEventSynchronize(ev[5]));
-    float hms = 0, kms = 0, dms = 0;
-    (void) hipEventElapsedTime(&hms, ev[0], ev[1]);
-    (void) hipEventElapsedTime(&kms, ev[2], ev[3]);
-    (void) hipEventElapsedTime(&dms, ev[4], ev[5]);
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));   // (the downloads have landed)
     if (stats) {
         stats->iterations = rounds;
-        stats->h2d_ms = hms;
-        stats->kernel_ms = kms;
-        stats->d2h_ms = dms;
         stats->edges_examined = grid_slots + tail_slots;
         stats->vertices_reached = queued;
     }

@@ -521,10 +521,8 @@ static int tc_count_part(gmx_graph_t* g, int part, int nparts, bool common_nbr_f
     dbuf<unsigned long long> ctr;   // [0] total, [1] nbig
     GMX_CHECK(ctr.alloc(2));
     GMX_HIP(hipMemset(ctr.p, 0, 2 * sizeof(unsigned long long)));
-    gmx_event ev0, ev1;
-    GMX_CHECK(ev0.create());
-    GMX_CHECK(ev1.create());
-    GMX_HIP(hipEventRecord(ev0, 0));
+    gmx_spans tm;
+    GMX_CHECK(tm.begin(tm.KERNEL));
     int64_t blocks = (nlocal + TC_THREADS - 1) / TC_THREADS;
     if (staged) {
         hipLaunchKernelGGL(tc_oriented_kernel, dim3(256 * 8), dim3(TCO_WAVES * 64), 0, 0, g->begin.p, g->node_idx.p,
@@ -556,17 +554,12 @@ static int tc_count_part(gmx_graph_t* g, int part, int nparts, bool common_nbr_f
                            g->begin.p, g->node_idx.p, g->V, g->E, nlocal, part, nparts, ctr.p);
         GMX_HIP(hipGetLastError());
     }
-    GMX_HIP(hipEventRecord(ev1, 0));
-    GMX_HIP(hipEventSynchronize(ev1));
-    float ms = 0;
-    (void) hipEventElapsedTime(&ms, ev0, ev1);
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.finish(stats));
     unsigned long long h = 0;
     GMX_HIP(hipMemcpy(&h, ctr.p, sizeof(h), hipMemcpyDeviceToHost));
     *count = (int64_t) h;
-    if (stats) {
-        stats->iterations = 1;
-        stats->kernel_ms = ms;
-    }
+    if (stats) stats->iterations = 1;
     return GMX_OK;
 }
 
@@ -830,9 +823,8 @@ extern "C" int gmx_adamic_adar(gmx_graph_t* g, double* aa_host, gmx_stats_t* sta
     size_t tb = 0;
     GMX_HIP(rocprim::exclusive_scan(nullptr, tb, groups.p, grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), 0));
     GMX_CHECK(tmp.alloc(tb));
-    gmx_event ev[4];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    gmx_spans tm;
+    GMX_CHECK(tm.begin(tm.KERNEL));
     GMX_HIP(hipMemsetAsync(ctr.p, 0, 2 * sizeof(unsigned long long), 0));
     GMX_HIP(hipMemsetAsync(groups.p + V, 0, sizeof(int64_t), 0));
     hipLaunchKernelGGL(aa_weight_kernel, dim3(tc_grid(V)), dim3(TC_THREADS), 0, 0, (const int32_t*) g->begin.p, V, w.p, groups.p);
@@ -841,20 +833,13 @@ extern "C" int gmx_adamic_adar(gmx_graph_t* g, double* aa_host, gmx_stats_t* sta
     hipLaunchKernelGGL(aa_rows_kernel, dim3(256 * 8), dim3(AA_WAVES * 64), 0, 0, (const int32_t*) g->begin.p, (const int32_t*) g->node_idx.p,
                        (const double*) w.p, (const int64_t*) grp_off.p, V, cap, alone, (const int32_t*) g->e_idx2idx.p, ctr.p, ctr.p + 1, aa.p);
     GMX_HIP(hipGetLastError());
-    GMX_HIP(hipEventRecord(ev[1], 0));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpy(aa_host, aa.p, sizeof(double) * (size_t) E, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));
     unsigned long long h = 0;
     GMX_HIP(hipMemcpy(&h, ctr.p + 1, sizeof(h), hipMemcpyDeviceToHost));
-    float kms = 0, dms = 0;
-    (void) hipEventElapsedTime(&kms, ev[0], ev[1]);
-    (void) hipEventElapsedTime(&dms, ev[2], ev[3]);
-    if (stats) {
-        stats->kernel_ms = kms;
-        stats->d2h_ms = dms;
-        stats->edges_examined = (int64_t) h;
-    }
+    if (stats) stats->edges_examined = (int64_t) h;
     return GMX_OK;
 }

@@ -418,25 +418,18 @@ static int tcd_count_part(gmx_graph_t* g, int part, int nparts, int64_t* count, 
     dbuf<unsigned long long> ctr;
     GMX_CHECK(ctr.alloc(TCD_NCTR));
     GMX_HIP(hipMemset(ctr.p, 0, TCD_NCTR * sizeof(unsigned long long)));
-    gmx_event ev0, ev1;
-    GMX_CHECK(ev0.create());
-    GMX_CHECK(ev1.create());
-    GMX_HIP(hipEventRecord(ev0, 0));
+    gmx_spans tm;
+    GMX_CHECK(tm.begin(tm.KERNEL));
     hipLaunchKernelGGL(tcd_count_kernel, dim3(256 * 8), dim3(TCD_WAVES * 64), 0, 0, (const int32_t*) p->out_begin.p, (const int32_t*) p->out_idx.p,
                        (const int32_t*) p->up_begin.p, (const int32_t*) p->up_idx.p, (const int64_t*) p->grp_off.p, p->V, part, nparts, cap, alone,
                        ratio, ctr.p);
     GMX_HIP(hipGetLastError());
-    GMX_HIP(hipEventRecord(ev1, 0));
-    GMX_HIP(hipEventSynchronize(ev1));
-    float ms = 0;
-    (void) hipEventElapsedTime(&ms, ev0, ev1);
+    GMX_CHECK(tm.end(tm.KERNEL));
+    GMX_CHECK(tm.finish(stats));
     unsigned long long h[TCD_NCTR];
     GMX_HIP(hipMemcpy(h, ctr.p, sizeof(h), hipMemcpyDeviceToHost));
     *count = (int64_t) h[TCD_TOTAL];
-    if (stats) {
-        stats->iterations = 1;
-        stats->kernel_ms = ms;
-    }
+    if (stats) stats->iterations = 1;
     if (getenv("GMX_TCD_LOG"))   // one line per call (tools/tcd_prof.py and the tests parse it)
         fprintf(stderr, "gmx triangle_counting_directed: plan V %lld out %lld up %lld order %s built %d build_ms %.3f; part %d/%d cap %d alone %d "
                         "ratio %d; items %llu staged + %llu memory; slots %llu alone + %llu list + %llu tail + %llu empty\n",

@@ -483,8 +483,7 @@ extern "C" int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host, int32_t* covere
     GMX_CHECK(select.alloc((size_t) E));
     GMX_CHECK(gmx_frontier_scan_alloc(&fs, (size_t) V, 0));
     GMX_CHECK(h_ctr.alloc(VC_NCTR));
-    gmx_event ev[4];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
 
     vc_state S;
     S.deg0 = p->deg0.p;
@@ -503,7 +502,7 @@ extern "C" int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host, int32_t* covere
     S.wave_min = (int32_t) wave_min;
     unsigned long long* h = h_ctr.p;
 
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     const double t_start = gmx_tick::now();
     GMX_HIP(hipMemsetAsync(ctr.p, 0, VC_NCTR * sizeof(unsigned long long), 0));
     GMX_HIP(hipMemsetAsync(select.p, 0, (size_t) E, 0));
@@ -591,20 +590,15 @@ extern "C" int gmx_v_cover(gmx_graph_t* g, uint8_t* select_host, int32_t* covere
         GMX_HIP(hipGetLastError());
     }
     GMX_CHECK(gmx_read_back(h_ctr, ctr.p, VC_NCTR));
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     const double t_finish = gmx_tick::now();
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpy(select_host, select.p, (size_t) E, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));
     *covered = (int32_t) h[VC_COVERED];
-    float ms = 0, cms = 0;
-    (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
-    (void) hipEventElapsedTime(&cms, ev[2], ev[3]);
     if (stats) {
         stats->iterations = round + tail_rounds;
-        stats->kernel_ms = ms;
-        stats->d2h_ms = cms;
         stats->edges_examined = (int64_t) (h[VC_SKIPS] + h[VC_EVALS] + h[VC_WALKS]);
         stats->vertices_reached = (int64_t) h[VC_COVERED];
         stats->edges_reached = kept;

@@ -423,8 +423,7 @@ extern "C" int gmx_random_walk_sampling(gmx_graph_t* g, float p_size, float p_ju
     GMX_HIP(rocprim::select(nullptr, b, rocprim::counting_iterator<int32_t>(0), l0.p, nsel.p, (size_t) V, rw_has_token{tok0.p}, 0));
     tmp_bytes = b > tmp_bytes ? b : tmp_bytes;
     GMX_CHECK(tmp.alloc(tmp_bytes));
-    gmx_event ev[4];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
 
     rw_state S;
     S.begin = g->begin.p;
@@ -441,7 +440,7 @@ extern "C" int gmx_random_walk_sampling(gmx_graph_t* g, float p_size, float p_ju
     int32_t* lb = l1.p;           // the touched list
     uint64_t x = *rng_state & RW_MASK;
 
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     const double t_start = gmx_tick::now();
     GMX_HIP(hipMemsetAsync(ctl.p, 0, sizeof(rw_ctl), 0));
     GMX_HIP(hipMemsetAsync(token, 0, sizeof(int32_t) * (size_t) V, 0));
@@ -556,23 +555,18 @@ extern "C" int gmx_random_walk_sampling(gmx_graph_t* g, float p_size, float p_ju
         }
     }
     if (in_tail && tail_launches) x = h->x;
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     const double t_end = gmx_tick::now();
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpyAsync(selected_host, selected.p, (size_t) V, hipMemcpyDeviceToHost, 0));
     if (token_host) GMX_HIP(hipMemcpyAsync(token_host, token, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost, 0));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));   // (the downloads have landed)
     *count = cnt;
     *rounds = grid_rounds + tail_rounds;
     *rng_state = x;
-    float kms = 0, dms = 0;
-    (void) hipEventElapsedTime(&kms, ev[0], ev[1]);
-    (void) hipEventElapsedTime(&dms, ev[2], ev[3]);
     if (stats) {
         stats->iterations = grid_rounds + tail_rounds;
-        stats->kernel_ms = kms;
-        stats->d2h_ms = dms;
         stats->edges_examined = (int64_t) (grid_rounds + tail_rounds) * T;
         stats->vertices_reached = cnt;
     }
@@ -600,8 +594,7 @@ extern "C" int gmx_node_sampling(gmx_graph_t* g, int by_degree, int32_t N, uint6
     GMX_CHECK(selected.alloc((size_t) V));
     GMX_CHECK(nsel.alloc(1));
     GMX_CHECK(h_nsel.alloc(1));
-    gmx_event ev[4];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
     rw_state S;
     S.begin = g->begin.p;
     S.node_idx = g->node_idx.p;
@@ -612,26 +605,21 @@ extern "C" int gmx_node_sampling(gmx_graph_t* g, int by_degree, int32_t N, uint6
     S.p_jump = 0;
     const uint64_t x = *rng_state & RW_MASK;
     const int nb = grid_for(V, RW_THREADS);
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     GMX_HIP(hipMemsetAsync(nsel.p, 0, sizeof(rw_word), 0));
     hipLaunchKernelGGL(rw_node_kernel, dim3(nb), dim3(RW_THREADS), 0, 0, S, x, rw_steps((uint64_t) nb * RW_THREADS), by_degree, (double) N,
                        (double) g->E, nsel.p);
     GMX_HIP(hipGetLastError());
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     GMX_CHECK(gmx_read_back(h_nsel, nsel.p));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpyAsync(selected_host, selected.p, (size_t) V, hipMemcpyDeviceToHost, 0));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));   // (the download has landed)
     *count = (int64_t) *h_nsel.p;
     *rng_state = rw_apply(rw_steps((uint64_t) V), x);
-    float kms = 0, dms = 0;
-    (void) hipEventElapsedTime(&kms, ev[0], ev[1]);
-    (void) hipEventElapsedTime(&dms, ev[2], ev[3]);
     if (stats) {
         stats->iterations = 1;
-        stats->kernel_ms = kms;
-        stats->d2h_ms = dms;
         stats->edges_examined = V;
         stats->vertices_reached = *count;
     }

@@ -262,8 +262,7 @@ extern "C" int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
     gmx_pinned<int64_t> h_m;
     GMX_CHECK(h_ctl.alloc());
     GMX_CHECK(h_m.alloc(2));
-    gmx_event ev[4];
-    for (gmx_event& e : ev) GMX_CHECK(e.create());
+    gmx_spans tm;
     gmx_event pev[5];
     if (phase_log)
         for (gmx_event& e : pev) GMX_CHECK(e.create());
@@ -272,7 +271,7 @@ extern "C" int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
     };
     const int gv = grid_for(V);
 
-    GMX_HIP(hipEventRecord(ev[0], 0));
+    GMX_CHECK(tm.begin(tm.KERNEL));
     GMX_HIP(hipMemsetAsync(ctl.p, 0, sizeof(wcc_ctl), 0));
     hipLaunchKernelGGL(wcc_init_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, parent.p, V);
     for (int r = 0; r < K; r++) {
@@ -327,12 +326,12 @@ extern "C" int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
     hipLaunchKernelGGL(wcc_max_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, (const int32_t*) size, V, ctl.p);
     GMX_HIP(hipGetLastError());
     phase_end(4);
-    GMX_HIP(hipEventRecord(ev[1], 0));
+    GMX_CHECK(tm.end(tm.KERNEL));
     GMX_CHECK(gmx_read_back(h_ctl, (const wcc_ctl*) ctl.p));
-    GMX_HIP(hipEventRecord(ev[2], 0));
+    GMX_CHECK(tm.begin(tm.D2H));
     GMX_HIP(hipMemcpy(comp_host, comp.p, sizeof(int32_t) * (size_t) V, hipMemcpyDeviceToHost));
-    GMX_HIP(hipEventRecord(ev[3], 0));
-    GMX_HIP(hipEventSynchronize(ev[3]));
+    GMX_CHECK(tm.end(tm.D2H));
+    GMX_CHECK(tm.finish(stats));
 
     unsigned long long sampled = 0, in_big = 0;
     for (int i = 0; i < BFS_SHARDS; i++) {
@@ -340,19 +339,14 @@ extern "C" int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
         in_big += h_ctl.p->shard[i].giant;
     }
     const int64_t largest = std::max((int64_t) in_big, (int64_t) h_ctl.p->largest);
-    float ms = 0, cms = 0;
-    GMX_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    GMX_HIP(hipEventElapsedTime(&cms, ev[2], ev[3]));
     if (num_comps) *num_comps = h_ctl.p->count;
     stats->iterations = K + 1;
     stats->vertices_reached = largest;
     stats->edges_examined = (int64_t) sampled + final_slots;
-    stats->kernel_ms = ms;
-    stats->d2h_ms = cms;
     if (phase_log) {
         static const char* const names[5] = {"sampling", "compress", "live", "final", "finish"};
         float t[5];
-        for (int i = 0; i < 5; i++) (void) hipEventElapsedTime(&t[i], i ? (hipEvent_t) pev[i - 1] : (hipEvent_t) ev[0], pev[i]);
+        for (int i = 0; i < 5; i++) (void) hipEventElapsedTime(&t[i], i ? (hipEvent_t) pev[i - 1] : tm.begin_event(tm.KERNEL), pev[i]);
         fprintf(stderr, "gmx wcc phases:");
         for (int i = 0; i < 5; i++) fprintf(stderr, " %s %.3f ms%s", names[i], t[i], i < 4 ? "," : "\n");
     }
