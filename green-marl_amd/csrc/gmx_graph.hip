@@ -399,6 +399,7 @@ void gmx_warm_modules() {
     gmx_touch_color();
     gmx_touch_close();
     gmx_touch_lcc();
+    gmx_touch_bicc();
 }
 
 static int check_sizes(int64_t V, int64_t E) {

@@ -357,6 +357,42 @@ int gmx_pr_multi_run(gmx_pr_multi* m, double e, double d, int32_t max_iter, void
 void gmx_pr_multi_free(gmx_pr_multi* m);
 bool gmx_pr_multi_verified(const gmx_pr_multi* m);   // false: the first exchange has not passed its check
 
+// ---- gmx_wcc's forest for the units that build on it (gmx_wcc.hip; gmx_bicc.hip)
+#ifdef __HIPCC__
+__device__ __forceinline__ int32_t wcc_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// link(u, v), from a = an ancestor of u (or u), b = one of v: while they differ, the larger is hooked under the smaller
+// if it still is a root.  THE MEMORY RULE: a plain load of parent[] may be served from a stale line in this CU's L1 or
+// this XCD's L2 while a wave on another XCD hooks.  A stale value is an older, still valid ancestor relation (trees only
+// merge, and equal ancestors mean "already one tree"), so the FIRST reads -- a and b, by the caller -- may be plain.  Every
+// retry must make progress from what the atomic returned (or from wcc_load, a relaxed agent-scope atomic load): a loop that
+// re-reads parent[] with plain loads can spin on a stale line for ever.  Here a step reads parent[hi] with wcc_load; a
+// root is hooked by the CAS, and where it is none (or the CAS lost) the pair becomes (parent[hi] < hi, lo): its maximum
+// falls with every step.  The climb is loads, not atomics: with a CAS at every step and no compress between the rounds, the
+// 5.4 M links of the second sampling round at RMAT-24 took 9.3 ms against 0.3 ms for the first round's 7.6 M (DESIGN.md
+// 4.2l) -- every climb through a big tree ends in atomics on the few vertices below its root.
+__device__ __forceinline__ void wcc_hook(int32_t* __restrict__ parent, int32_t a, int32_t b) {
+    while (a != b) {
+        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        int32_t p = wcc_load(&parent[hi]);
+        if (p == hi) {
+            p = atomicCAS(&parent[hi], hi, lo);
+            if (p == hi) break;
+        }
+        a = p;
+        b = lo;
+    }
+}
+#endif
+// gmx_wcc's device part up to its last compress, on stream 0 and with gmx_wcc's knobs: parent[V] (device, the caller's)
+// ends as parent[v] = the smallest vertex of v's weak component.  V > 0; temporaries come from the workspace and go back.
+int gmx_wcc_forest(gmx_graph* g, int32_t* parent);
+// parent[v] = the root of v, for a forest hooked by wcc_hook (enqueued on stream 0)
+int gmx_wcc_compress(int32_t* parent, int64_t V);
+// gmx_wcc's finish on such a forest: compress, then comp[v] (device) = the rank of v's root among the roots in id order
+// and *count (device) = the roots.  flag, rank: V words of scratch each.  Enqueued on stream 0.
+int gmx_wcc_canon(int32_t* parent, int64_t V, int32_t* flag, int32_t* rank, int32_t* comp, int32_t* count);
+
 // GMX_PLAN_TIMING=1: where a plan build spends its time (synchronises at every mark)
 struct gmx_tick {
     bool on;
@@ -394,6 +430,7 @@ void gmx_touch_msf();
 void gmx_touch_color();
 void gmx_touch_close();
 void gmx_touch_lcc();
+void gmx_touch_bicc();
 void gmx_warm_modules();   // once per process: load every translation unit's code object (see gmx_touch_*)
 
 static inline int gmx_bits_for(int64_t v) {  // bits needed to represent values in [0, v)

@@ -43,31 +43,6 @@ struct wcc_ctl {
     } shard[BFS_SHARDS];
 };
 
-__device__ __forceinline__ int32_t wcc_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// link(u, v), from a = an ancestor of u (or u), b = one of v: while they differ, the larger is hooked under the smaller
-// if it still is a root.  THE MEMORY RULE: a plain load of parent[] may be served from a stale line in this CU's L1 or
-// this XCD's L2 while a wave on another XCD hooks.  A stale value is an older, still valid ancestor relation (trees only
-// merge, and equal ancestors mean "already one tree"), so the FIRST reads -- a and b, by the caller -- may be plain.  Every
-// retry must make progress from what the atomic returned (or from wcc_load, a relaxed agent-scope atomic load): a loop that
-// re-reads parent[] with plain loads can spin on a stale line for ever.  Here a step reads parent[hi] with wcc_load; a
-// root is hooked by the CAS, and where it is none (or the CAS lost) the pair becomes (parent[hi] < hi, lo): its maximum
-// falls with every step.  The climb is loads, not atomics: with a CAS at every step and no compress between the rounds, the
-// 5.4 M links of the second sampling round at RMAT-24 took 9.3 ms against 0.3 ms for the first round's 7.6 M (DESIGN.md
-// 4.2l) -- every climb through a big tree ends in atomics on the few vertices below its root.
-__device__ __forceinline__ void wcc_hook(int32_t* __restrict__ parent, int32_t a, int32_t b) {
-    while (a != b) {
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        int32_t p = wcc_load(&parent[hi]);
-        if (p == hi) {
-            p = atomicCAS(&parent[hi], hi, lo);
-            if (p == hi) break;
-        }
-        a = p;
-        b = lo;
-    }
-}
-
 __global__ void __launch_bounds__(WCC_THREADS) wcc_init_kernel(int32_t* __restrict__ parent, int64_t V) {
     for (int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; v < V; v += (int64_t) gridDim.x * blockDim.x) parent[v] = (int32_t) v;
 }
@@ -229,62 +204,59 @@ __global__ void __launch_bounds__(WCC_THREADS) wcc_max_kernel(const int32_t* __r
     }
 }
 
-extern "C" int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, gmx_stats_t* stats_out) {
-    GMX_REQUIRE(g && comp_host, "NULL argument");
-    gmx_stats_t local_stats;
-    gmx_stats_t* stats = stats_out ? stats_out : &local_stats;
-    memset(stats, 0, sizeof(*stats));
-    if (num_comps) *num_comps = 0;
-    const int64_t V = g->V, E = g->E;
-    if (V == 0) return GMX_OK;
-    const int K = (int) gmx_env_int("GMX_WCC_SAMPLE_ROUNDS", 2, 0, WCC_MAX_ROUNDS);
-    const bool skip = g->has_reverse && gmx_env_int("GMX_WCC_SKIP", 1, -1, 1) != 0;
-    const int32_t forced = (int32_t) gmx_env_int("GMX_WCC_GIANT", -1, -1, V - 1);
-    const bool phase_log = getenv("GMX_WCC_PHASES") != nullptr;   // per-phase times (events) for tools/wcc_prof.py
-
-    gmx_ws_scope scope;
-    wbuf<int32_t> parent, list, flag, rank, comp;
+// what the forest needs besides parent[]: the knobs (read at every call), the live list, the control block and its mirror
+struct wcc_work {
+    int K = 0;
+    bool skip = false;
+    int32_t forced = -1;
+    wbuf<int32_t> list;
     wbuf<wcc_ctl> ctl;
-    wbuf<char> scan_tmp;
-    GMX_CHECK(parent.alloc(V));
-    GMX_CHECK(list.alloc(V));
-    GMX_CHECK(flag.alloc(V));
-    GMX_CHECK(rank.alloc(V));
-    GMX_CHECK(comp.alloc(V));
-    GMX_CHECK(ctl.alloc(1));
-    size_t scan_bytes = 0;
-    GMX_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, flag.p, rank.p, 0, (size_t) V, rocprim::plus<int32_t>(), 0));
-    GMX_CHECK(scan_tmp.alloc(scan_bytes));
     frontier_scan fs[2];
-    GMX_CHECK(gmx_frontier_scan_alloc(&fs[0], (size_t) V, 0));
-    if (skip) GMX_CHECK(gmx_frontier_scan_alloc(&fs[1], (size_t) V, 0));
     gmx_pinned<wcc_ctl> h_ctl;
     gmx_pinned<int64_t> h_m;
-    GMX_CHECK(h_ctl.alloc());
-    GMX_CHECK(h_m.alloc(2));
-    gmx_spans tm;
-    gmx_event pev[5];
-    if (phase_log)
-        for (gmx_event& e : pev) GMX_CHECK(e.create());
-    auto phase_end = [&](int ph) {
-        if (phase_log) (void) hipEventRecord(pev[ph], 0);
-    };
+    int64_t live = 0, final_slots = 0;   // results: live vertices, slots of the final pass
+    int alloc(const gmx_graph* g) {
+        const int64_t V = g->V;
+        K = (int) gmx_env_int("GMX_WCC_SAMPLE_ROUNDS", 2, 0, WCC_MAX_ROUNDS);
+        skip = g->has_reverse && gmx_env_int("GMX_WCC_SKIP", 1, -1, 1) != 0;
+        forced = (int32_t) gmx_env_int("GMX_WCC_GIANT", -1, -1, V - 1);
+        GMX_CHECK(list.alloc(V));
+        GMX_CHECK(ctl.alloc(1));
+        GMX_CHECK(gmx_frontier_scan_alloc(&fs[0], (size_t) V, 0));
+        if (skip) GMX_CHECK(gmx_frontier_scan_alloc(&fs[1], (size_t) V, 0));
+        GMX_CHECK(h_ctl.alloc());
+        GMX_CHECK(h_m.alloc(2));
+        return GMX_OK;
+    }
+};
+
+// sampling, compress, giant, live list and the final pass on parent[V]: every component is one tree in the end, its root
+// its smallest vertex (the trees are not compressed yet).  phase_end(i) marks the end of phase i = 0 .. 3.
+template <class PhaseEnd>
+static int wcc_forest(gmx_graph* g, wcc_work& W, int32_t* parent, PhaseEnd phase_end) {
+    const int64_t V = g->V, E = g->E;
+    const int K = W.K;
+    const bool skip = W.skip;
+    wbuf<int32_t>& list = W.list;
+    wbuf<wcc_ctl>& ctl = W.ctl;
+    frontier_scan* fs = W.fs;
+    gmx_pinned<wcc_ctl>& h_ctl = W.h_ctl;
+    gmx_pinned<int64_t>& h_m = W.h_m;
     const int gv = grid_for(V);
 
-    GMX_CHECK(tm.begin(tm.KERNEL));
     GMX_HIP(hipMemsetAsync(ctl.p, 0, sizeof(wcc_ctl), 0));
-    hipLaunchKernelGGL(wcc_init_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, parent.p, V);
+    hipLaunchKernelGGL(wcc_init_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, parent, V);
     for (int r = 0; r < K; r++) {
         // (a compress between the rounds as well: a round then starts from roots, and most of its links end at the two loads)
-        if (r > 0) hipLaunchKernelGGL(wcc_compress_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, parent.p, V);
+        if (r > 0) hipLaunchKernelGGL(wcc_compress_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, parent, V);
         hipLaunchKernelGGL(wcc_sample_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, (const int32_t*) g->begin.p, (const int32_t*) g->node_idx.p, V, (int32_t) r,
-                           parent.p, ctl.p);
+                           parent, ctl.p);
     }
     phase_end(0);
-    if (K > 0) hipLaunchKernelGGL(wcc_compress_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, parent.p, V);
+    if (K > 0) hipLaunchKernelGGL(wcc_compress_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, parent, V);
     phase_end(1);
-    hipLaunchKernelGGL(wcc_giant_kernel, dim3(1), dim3(WCC_PROBES), 0, 0, (const int32_t*) parent.p, V, forced, ctl.p);
-    hipLaunchKernelGGL(wcc_live_kernel, dim3(grid_for(V, BFS_ITEMS)), dim3(WCC_THREADS), 0, 0, (const int32_t*) parent.p, (const int32_t*) g->begin.p,
+    hipLaunchKernelGGL(wcc_giant_kernel, dim3(1), dim3(WCC_PROBES), 0, 0, (const int32_t*) parent, V, W.forced, ctl.p);
+    hipLaunchKernelGGL(wcc_live_kernel, dim3(grid_for(V, BFS_ITEMS)), dim3(WCC_THREADS), 0, 0, (const int32_t*) parent, (const int32_t*) g->begin.p,
                        (const int32_t*) g->r_begin.p, V, skip ? 0 : 1, ctl.p, list.p);
     GMX_HIP(hipGetLastError());
     int64_t n = V, live = V;   // rows listed, live vertices
@@ -310,11 +282,54 @@ extern "C" int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
             final_slots += m;
             if (m > 0)
                 hipLaunchKernelGGL(wcc_final_kernel, dim3((unsigned) nb), dim3(WCC_THREADS), 0, 0, begs[d], idxs[d], (const int32_t*) list.p, n,
-                                   (const int64_t*) fs[d].off.p, m, parent.p);
+                                   (const int64_t*) fs[d].off.p, m, parent);
         }
         GMX_HIP(hipGetLastError());
     }
     phase_end(3);
+    W.live = live;
+    W.final_slots = final_slots;
+    return GMX_OK;
+}
+
+extern "C" int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, gmx_stats_t* stats_out) {
+    GMX_REQUIRE(g && comp_host, "NULL argument");
+    gmx_stats_t local_stats;
+    gmx_stats_t* stats = stats_out ? stats_out : &local_stats;
+    memset(stats, 0, sizeof(*stats));
+    if (num_comps) *num_comps = 0;
+    const int64_t V = g->V, E = g->E;
+    if (V == 0) return GMX_OK;
+    const bool phase_log = getenv("GMX_WCC_PHASES") != nullptr;   // per-phase times (events) for tools/wcc_prof.py
+
+    gmx_ws_scope scope;
+    wbuf<int32_t> parent, flag, rank, comp;
+    wbuf<char> scan_tmp;
+    wcc_work W;
+    GMX_CHECK(parent.alloc(V));
+    GMX_CHECK(W.alloc(g));
+    GMX_CHECK(flag.alloc(V));
+    GMX_CHECK(rank.alloc(V));
+    GMX_CHECK(comp.alloc(V));
+    wbuf<int32_t>& list = W.list;
+    wbuf<wcc_ctl>& ctl = W.ctl;
+    gmx_pinned<wcc_ctl>& h_ctl = W.h_ctl;
+    const int K = W.K;
+    size_t scan_bytes = 0;
+    GMX_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, flag.p, rank.p, 0, (size_t) V, rocprim::plus<int32_t>(), 0));
+    GMX_CHECK(scan_tmp.alloc(scan_bytes));
+    gmx_spans tm;
+    gmx_event pev[5];
+    if (phase_log)
+        for (gmx_event& e : pev) GMX_CHECK(e.create());
+    auto phase_end = [&](int ph) {
+        if (phase_log) (void) hipEventRecord(pev[ph], 0);
+    };
+    const int gv = grid_for(V);
+
+    GMX_CHECK(tm.begin(tm.KERNEL));
+    GMX_CHECK(wcc_forest(g, W, parent.p, phase_end));
+    const int64_t live = W.live, final_slots = W.final_slots;
     // finish: roots, ranks, comp, sizes (the list's memory is free now)
     int32_t* size = list.p;
     hipLaunchKernelGGL(wcc_compress_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, parent.p, V);
@@ -355,6 +370,42 @@ extern "C" int gmx_wcc(gmx_graph_t* g, int32_t* comp_host, int64_t* num_comps, g
                 "gmx wcc: V %lld E %lld sample_rounds %d sampled %llu giant %d skipped %lld live %lld reverse %d final_slots %lld comps %d largest %lld\n",
                 (long long) V, (long long) E, K, sampled, (int) h_ctl.p->gstar, (long long) (V - live), (long long) live, g->has_reverse ? 1 : 0,
                 (long long) final_slots, (int) h_ctl.p->count, (long long) largest);
+    return GMX_OK;
+}
+
+// ---- the forest and the finish for other units (gmx_internal.h)
+int gmx_wcc_forest(gmx_graph* g, int32_t* parent) {
+    gmx_ws_scope scope;
+    wcc_work W;
+    GMX_CHECK(W.alloc(g));
+    GMX_CHECK(wcc_forest(g, W, parent, [](int) {}));
+    return gmx_wcc_compress(parent, g->V);
+}
+int gmx_wcc_compress(int32_t* parent, int64_t V) {
+    hipLaunchKernelGGL(wcc_compress_kernel, dim3(grid_for(V)), dim3(WCC_THREADS), 0, 0, parent, V);
+    GMX_HIP(hipGetLastError());
+    return GMX_OK;
+}
+// comp[v] = rank of v's root, *count = the roots (wcc_comp_kernel without the sizes)
+__global__ void __launch_bounds__(WCC_THREADS) wcc_canon_kernel(const int32_t* __restrict__ parent, const int32_t* __restrict__ rank,
+                                                                const int32_t* __restrict__ flag, int64_t V, int32_t* __restrict__ comp,
+                                                                int32_t* __restrict__ count) {
+    for (int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; v < V; v += (int64_t) gridDim.x * blockDim.x) {
+        comp[v] = rank[parent[v]];
+        if (v == V - 1) *count = rank[v] + flag[v];
+    }
+}
+int gmx_wcc_canon(int32_t* parent, int64_t V, int32_t* flag, int32_t* rank, int32_t* comp, int32_t* count) {
+    const int gv = grid_for(V);
+    size_t scan_bytes = 0;
+    GMX_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, flag, rank, 0, (size_t) V, rocprim::plus<int32_t>(), 0));
+    wbuf<char> scan_tmp;
+    GMX_CHECK(scan_tmp.alloc(scan_bytes));   // (the caller's workspace scope)
+    GMX_CHECK(gmx_wcc_compress(parent, V));
+    hipLaunchKernelGGL(wcc_flag_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, (const int32_t*) parent, V, flag);
+    GMX_HIP(rocprim::exclusive_scan((void*) scan_tmp.p, scan_bytes, flag, rank, 0, (size_t) V, rocprim::plus<int32_t>(), 0));
+    hipLaunchKernelGGL(wcc_canon_kernel, dim3(gv), dim3(WCC_THREADS), 0, 0, (const int32_t*) parent, (const int32_t*) rank, (const int32_t*) flag, V, comp, count);
+    GMX_HIP(hipGetLastError());
     return GMX_OK;
 }
 

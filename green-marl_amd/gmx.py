@@ -55,7 +55,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_biconnected", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -149,6 +149,7 @@ def lib():
         L.gmx_triangle_counting_directed.argtypes = [vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_triangle_counting_directed_part.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_clustering.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_biconnected.argtypes = [vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_bfs_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
         L.gmx_bfs_free.argtypes = [vp]
         L.gmx_bfs_start.argtypes = [vp, i32]
@@ -718,6 +719,25 @@ class Graph:
                                  C.byref(T), C.byref(W), C.byref(st)))
         V = self.V
         return (t[:V] if tri else None, d[:V] if deg else None, c[:V] if lcc else None, int(T.value), int(W.value), st.as_dict())
+
+    def biconnected(self, bridges=True, artic=True, blocks=True, tecc=True):
+        """Bridges, articulation points, biconnected components and 2-edge-connected components of the stored slots read as an
+        undirected simple graph -- returns (bridge[bool, E] and block[int32, E] by uploaded forward slot, artic[bool, V],
+        tecc[int32, V], in the order bridge, artic, block, tecc, then num_blocks, num_bridges, num_artic, num_tecc, stats); an
+        array not asked for is None and is not built.  block is -1 at self-loop slots, its ids increase with each block's
+        smallest uploaded slot; tecc is numbered as wcc() numbers components.  Any row order; needs the reverse CSR (gmx.h:
+        GMX_BICC_*)."""
+        V, E = self.V, self.E
+        br = np.zeros(max(E, 1), np.uint8) if bridges else None
+        ar = np.zeros(max(V, 1), np.uint8) if artic else None
+        bl = np.full(max(E, 1), -1, np.int32) if blocks else None
+        te = np.zeros(max(V, 1), np.int32) if tecc else None
+        n = [C.c_int64(0) for _ in range(4)]
+        st = Stats()
+        _ck(lib().gmx_biconnected(self._h, br.ctypes.data if bridges else None, ar.ctypes.data if artic else None, bl.ctypes.data if blocks else None,
+                                  te.ctypes.data if tecc else None, C.byref(n[0]), C.byref(n[1]), C.byref(n[2]), C.byref(n[3]), C.byref(st)))
+        return (br[:E].astype(bool) if bridges else None, ar[:V].astype(bool) if artic else None, bl[:E] if blocks else None,
+                te[:V] if tecc else None, int(n[0].value), int(n[1].value), int(n[2].value), int(n[3].value), st.as_dict())
 
 
 def closeness_of(far, reach, wasserman_faust=False):

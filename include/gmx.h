@@ -732,6 +732,48 @@ int gmx_triangle_counting_directed_part(gmx_graph_t* g, int part, int nparts, in
  * edges_examined = |UP'| (the undirected edges), vertices_reached = vertices with tri > 0, d2h_ms = the downloads. */
 int gmx_clustering(gmx_graph_t* g, int64_t* tri_host, int32_t* deg_host, double* lcc_host, int64_t* triangles, int64_t* wedges, gmx_stats_t* stats);
 
+/* Bridges, articulation points, biconnected components (blocks) and 2-edge-connected components (the reference has no
+ * such program).  As gmx_clustering reads it, the stored slots form an undirected simple graph: every forward slot u -> w
+ * with u != w denotes the edge {u, w}, w -> u and repeats of either denote the same edge, self-loop slots are read and
+ * ignored.  Any row order.  The entry walks out-rows and in-rows, so it needs the reverse CSR: GMX_ERR_STATE on a
+ * GMX_GRAPH_NO_REVERSE graph.  Nothing is cached on the graph.
+ * bridge_host[E], by UPLOADED forward slot: 1 when the slot's edge is a bridge (its removal disconnects its component);
+ * every slot of that edge gets it, self-loop slots get 0.  *num_bridges counts undirected edges, not slots.
+ * artic_host[V]: 1 when removing v raises the number of components.  *num_artic = their number.
+ * block_host[E], by uploaded slot: the biconnected component of the slot's edge, -1 for a self-loop slot.  The ids are
+ * dense over 0 .. *num_blocks - 1 and increase with each block's smallest uploaded slot, so they are identical between a
+ * verbatim upload and a sorting upload of the same arrays.
+ * tecc_host[V]: the 2-edge-connected component of v -- its component once the bridges are removed -- numbered exactly as
+ * gmx_wcc numbers components: dense, by smallest vertex, an isolated vertex its own component.  *num_tecc = their number
+ * = the weak components + *num_bridges.
+ * The result is unique: all arrays are exact and byte-identical from run to run and under every knob below.
+ * g == NULL: GMX_ERR_ARG before any device call.  Every output pointer and stats may be NULL; an array that is NULL is
+ * neither built nor downloaded.  V = 0: GMX_OK with all counts 0.  E = 0: no blocks, tecc is the identity.
+ * Method (it fixes the statistics): the roots are the smallest vertex of every weak component (gmx_wcc's forest).  One
+ * level-synchronous BFS from all roots over out-rows and in-rows gives level[] and par[w] = the smallest vertex of the
+ * previous level with a slot to w.  Every forward slot u -> w that is no self loop and no tree slot (par[u] != w and
+ * par[w] != u) then walks its tree cycle: of the two cursors x = u, y = w the one of the greater level (x on a tie) has
+ * its tree edge joined to the class of the walk's first edge and moves to its parent, until they meet.  The classes of
+ * tree edges are the blocks; a tree edge alone in its class is a bridge.  A cursor may jump: skip[v] = t records that all
+ * tree edges from v up to its ancestor t are in one class, written by every walk for the vertices it moved from.
+ * stats: iterations = levels of the spanning forest (max level + 1), vertices_reached = tree edges = V - weak components,
+ * edges_examined = cursor moves of the walks (`steps`: with GMX_BICC_SKIP=0 exactly the sum over the walked slots of the
+ * two path lengths to the lowest common ancestor, else a number that depends on the order of the walks), kernel_ms =
+ * device time from the first launch to the last, d2h_ms = the downloads, h2d_ms = 0.
+ * Read at every call, no result byte depends on them:
+ *   GMX_BICC_TAIL    one workgroup runs the BFS levels while the level's rows hold at most this many slots; 0: never;
+ *                    default 1024,
+ *   GMX_BICC_SKIP    0: no jumps and no skip[] writes; default 1,
+ *   GMX_BICC_WALKS   at most this many forward slots per walk launch, in device slot order, so that later walks see the
+ *                    facts of earlier ones; 0: one launch; default 1048576,
+ *   GMX_BICC_LOG     one line per call on stderr: `gmx bicc: V <V> E <E> levels <l> roots <r> tree <t> walks <w> steps <s>
+ *                    jumps <j> links <k> grid_levels <g> tail_levels <t> blocks <b> bridges <b> artic <a> tecc <c>`, with
+ *                    g + t = l = iterations, tree = vertices_reached, steps = edges_examined, walks = the walked slots,
+ *                    links = the joins that found two different class roots; a count that was not asked for is -1,
+ *   GMX_BICC_PHASES  the device time of forest, walks and finish on stderr (tools/bicc_prof.py). */
+int gmx_biconnected(gmx_graph_t* g, uint8_t* bridge_host, uint8_t* artic_host, int32_t* block_host, int32_t* tecc_host, int64_t* num_blocks,
+                    int64_t* num_bridges, int64_t* num_artic, int64_t* num_tecc, gmx_stats_t* stats);
+
 /* The common-neighbour iterator, gm_common_neighbor_iter(G, s, d) (gm_common_neighbor_iter.cc:21-44): the slots of s's
  * row, in order and with their multiplicity, whose value occurs in d's row (Foreach(u: s.CommonNbrs(d)) <=>
  * Foreach(u: s.Nbrs)(d.isNbr(u)), gm_common_neighbor_iter.h:11-17).  gmx_common_nbrs lists them for one pair (*n = how
