@@ -400,6 +400,7 @@ void gmx_warm_modules() {
     gmx_touch_close();
     gmx_touch_lcc();
     gmx_touch_bicc();
+    gmx_touch_ktruss();
 }
 
 static int check_sizes(int64_t V, int64_t E) {

@@ -1,4 +1,4 @@
-// gmx_tcd_plan.h -- the plan gmx_tcd.hip builds from the forward CSR, shared with gmx_lcc.hip (gmx_clustering).
+// gmx_tcd_plan.h -- the plan gmx_tcd.hip builds from the forward CSR, shared with gmx_lcc.hip (gmx_clustering) and gmx_ktruss.hip (gmx_ktruss).
 #ifndef GMX_TCD_PLAN_H_
 #define GMX_TCD_PLAN_H_
 
@@ -18,6 +18,14 @@ struct tcd_plan {
     int64_t hubs = 0;           // the `hubs` highest plan ids, a multiple of 64 ...
     dbuf<uint32_t> hub_bits;    // ... and UP' among them as a hubs x hubs bit matrix: row u - (V - hubs), bit w - (V - hubs)
     double hub_ms = 0;
+    // gmx_ktruss's additions, built on its first call on the plan (gmx_ktruss.hip) and freed with it: the symmetric adjacency
+    // in plan ids, row v = DOWN'(v) then UP'(v) (sorted as it stands), with the edge id -- the position in up_idx -- of
+    // every slot, and the lower end of every edge id
+    bool kt_ready = false;
+    dbuf<int32_t> nb_begin;     // [V + 1]
+    dbuf<int32_t> nb_idx;       // [2 E_up]
+    dbuf<int32_t> nb_eid;       // [2 E_up]
+    dbuf<int32_t> up_src;       // [E_up]: the row of edge id e in UP'
 };
 
 // builds the plan of g (gmx_tcd.hip); the caller owns *out (gmx_tcd_plan_free)

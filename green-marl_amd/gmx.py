@@ -55,7 +55,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_biconnected", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_biconnected", "gmx_ktruss", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -150,6 +150,7 @@ def lib():
         L.gmx_triangle_counting_directed_part.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_clustering.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_biconnected.argtypes = [vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_ktruss.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_bfs_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
         L.gmx_bfs_free.argtypes = [vp]
         L.gmx_bfs_start.argtypes = [vp, i32]
@@ -738,6 +739,22 @@ class Graph:
                                   te.ctypes.data if tecc else None, C.byref(n[0]), C.byref(n[1]), C.byref(n[2]), C.byref(n[3]), C.byref(st)))
         return (br[:E].astype(bool) if bridges else None, ar[:V].astype(bool) if artic else None, bl[:E] if blocks else None,
                 te[:V] if tecc else None, int(n[0].value), int(n[1].value), int(n[2].value), int(n[3].value), st.as_dict())
+
+    def ktruss(self, truss=True, support=True):
+        """k-truss decomposition and per-edge triangle support of the stored slots read as an undirected simple graph -- returns
+        (truss[int32, E], support[int32, E], max_truss, num_edges, stats), both arrays by uploaded forward slot; an array not
+        asked for is None and is not built.  support[e] is the number of triangles through the slot's edge, truss[e] the largest
+        k such that the edge lies in a subgraph whose every edge is in at least k - 2 triangles of that subgraph (at least 2);
+        every slot of one undirected edge carries the same values and a self-loop slot carries 0.  max_truss is the largest
+        truss number, num_edges the number of undirected edges, stats["vertices_reached"] the edges of the largest truss number
+        and stats["iterations"] the peeling rounds.  truss=False is the cheap triangles-per-edge query: nothing is peeled and
+        max_truss is 0.  Forward CSR only, any row order (gmx.h: GMX_KTRUSS_*)."""
+        E = self.E
+        t = np.zeros(max(E, 1), np.int32) if truss else None
+        s = np.zeros(max(E, 1), np.int32) if support else None
+        k, n, st = C.c_int32(0), C.c_int64(0), Stats()
+        _ck(lib().gmx_ktruss(self._h, t.ctypes.data if truss else None, s.ctypes.data if support else None, C.byref(k), C.byref(n), C.byref(st)))
+        return (t[:E] if truss else None, s[:E] if support else None, int(k.value), int(n.value), st.as_dict())
 
 
 def closeness_of(far, reach, wasserman_faust=False):

@@ -774,6 +774,65 @@ int gmx_clustering(gmx_graph_t* g, int64_t* tri_host, int32_t* deg_host, double*
 int gmx_biconnected(gmx_graph_t* g, uint8_t* bridge_host, uint8_t* artic_host, int32_t* block_host, int32_t* tecc_host, int64_t* num_blocks,
                     int64_t* num_bridges, int64_t* num_artic, int64_t* num_tecc, gmx_stats_t* stats);
 
+/* k-truss decomposition and per-edge triangle support (the reference has no such program).  The stored slots are read
+ * exactly as gmx_clustering reads them, N(v) = { u != v : v -> u or u -> v is stored }: self loops and repeated slots change
+ * nothing, rows may be in any order, and only the forward CSR is read (a GMX_GRAPH_NO_REVERSE graph works; there is no
+ * GMX_ERR_STATE).
+ * support_host[E], by UPLOADED forward slot: |N(u) & N(w)| for the slot u -> w, the triangles through its edge.  Every slot
+ * of one undirected edge gets the same value, in either direction and including repeats; self-loop slots get 0.
+ * truss_host[E], by uploaded slot: the truss number of the slot's edge, the largest k such that the edge lies in a subgraph
+ * in which every edge is in at least k - 2 triangles of that subgraph: at least 2 for every real edge, 0 for a self-loop
+ * slot.  *max_truss = the largest truss number (0 when there is no edge), *num_edges = the undirected edges.
+ * Each array may be NULL and is then neither built nor downloaded.  truss_host == NULL means no peeling at all: the call
+ * stops after the support phase (the cheap "triangles per edge" query), *max_truss = 0 and iterations = 0.  With both NULL
+ * only *num_edges is produced.  num_edges and stats may be NULL.
+ * g == NULL, or max_truss == NULL (checked before g is touched): GMX_ERR_ARG before any device call.  V = 0: GMX_OK, no array
+ * is written, the counts are 0.  E = 0 or self loops only: GMX_OK, zero arrays, answered without a plan.  When the plan's
+ * additions or the call's per-edge scratch cannot be allocated: GMX_ERR_NOMEM, and the message gives the byte count.  More
+ * than 2^30 - 1 undirected edges: GMX_ERR_ARG (the symmetric adjacency has 32-bit offsets).
+ * The device uses integers only; truss numbers are unique by definition and support is a count: both arrays are
+ * byte-identical from run to run and under every knob, and between a verbatim and a sorting upload of the same arrays.
+ * Method (it fixes the statistics):
+ *   plan     gmx_triangle_counting_directed's and gmx_clustering's, cached on the graph and shared with both (whichever entry
+ *            is called first builds it; GMX_KTRUSS_NO_ORDER, GMX_LCC_NO_ORDER and GMX_TCD_NO_ORDER each rebuild a cached
+ *            plan of the other order).  The edge id of an undirected edge is its position in the plan's upper lists.  The
+ *            first gmx_ktruss call adds the symmetric adjacency in plan ids with the edge id of every slot, built from the
+ *            upper lists with one device sort, and frees it with the plan.
+ *   support  one work item per edge id: the shorter row of its two ends is walked, the longer one binary-searched; no atomics.
+ *   peeling  synchronous rounds over one word sup[e] per edge that only falls by atomic decrements, and a round stamp per
+ *            edge ("not queued", or the round that removes it).  A level's value s is the smallest sup among the live edges
+ *            (levels jump to it, as gmx_kcore's do); round 0 of a level stamps and queues every live edge with sup <= s.  A
+ *            round processes its queue: every queued edge e = {a, b} gets truss s + 2, and for every x in N(a) & N(b), with
+ *            e1 = {a, x} and e2 = {b, x} (the shorter row is walked -- ties: the lower plan id -- the longer one searched),
+ *            the triangle still exists when neither e1 nor e2 was removed in an EARLIER round.  Then: both in this round's
+ *            queue: nothing; only e1: e2 is decremented iff id(e) < id(e1), and symmetrically; neither: both are
+ *            decremented.  Each vanishing triangle so decrements each surviving edge exactly once.  The decrement that
+ *            returns s + 1 stamps the edge with the next round and appends it to the next queue, exactly once; edges already
+ *            queued for the next round keep being decremented.  When a round queues nothing, a compacting scan of the live
+ *            list finds the next s.  Rounds that removed something are numbered 0, 1, 2, ... across the run; they are
+ *            separated by a kernel boundary or, in the one-workgroup tail, by a barrier.  The queue's rows go through the
+ *            merge-path tile (in the tail: a wave per row); a queue entry is the end with the shorter row.
+ * Every loop ends by construction: no kernel waits for a value another workgroup writes, a tail launch returns to the host
+ * when its queue outgrows its capacity or no edge is left, and the host loop is bounded by "every level removes at least one
+ * edge" (a level that queues nothing is GMX_ERR_HIP).
+ * stats: iterations = rounds that removed something, vertices_reached = undirected edges with truss == *max_truss,
+ * edges_examined = slots of the shorter rows walked by the removals = the sum over the edges of min(deg(a), deg(b)),
+ * independent of order and knobs (0 without peeling), kernel_ms = device time from the first launch after the plan to the
+ * last (the plan and its additions are graph preprocessing), d2h_ms = the downloads, h2d_ms = 0.
+ * Read at every call, no result byte depends on them:
+ *   GMX_KTRUSS_NO_ORDER=1  the plan keeps the graph's numbering;
+ *   GMX_KTRUSS_TAIL        one workgroup runs the rounds (and the level scans between them) while the queue's rows hold at most
+ *                          this many slots; 0: never; default 1024, taken over from gmx_kcore (flat from 0 to 4096 on RMAT-20);
+ *   GMX_KTRUSS_LOG         one line per call on stderr: `gmx ktruss: plan V <V> E <E> up <|UP'|> order <degree|identity>
+ *                          built <0|1> adj_built <0|1>; support plain triangles <T>; levels <l> rounds <r> scanned <n>
+ *                          grid_rounds <g> tail_rounds <t> slots <s> max_truss <k> top <n>`, with g + t = r = iterations, slots =
+ *                          edges_examined, top = vertices_reached, T = the sum of the supports / 3 and scanned = the entries of
+ *                          the live lists the level scans read (no line when the call is answered without a plan or with
+ *                          both arrays NULL);
+ *   GMX_KTRUSS_PHASES      the device time of the plan additions, support, level scans, grid rounds, tail launches and finish, and the
+ *                          largest number of decrements one edge received, on stderr (tools/ktruss_prof.py). */
+int gmx_ktruss(gmx_graph_t* g, int32_t* truss_host, int32_t* support_host, int32_t* max_truss, int64_t* num_edges, gmx_stats_t* stats);
+
 /* The common-neighbour iterator, gm_common_neighbor_iter(G, s, d) (gm_common_neighbor_iter.cc:21-44): the slots of s's
  * row, in order and with their multiplicity, whose value occurs in d's row (Foreach(u: s.CommonNbrs(d)) <=>
  * Foreach(u: s.Nbrs)(d.isNbr(u)), gm_common_neighbor_iter.h:11-17).  gmx_common_nbrs lists them for one pair (*n = how
