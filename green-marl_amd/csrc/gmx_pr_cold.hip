@@ -1360,6 +1360,10 @@ int pr_cold_create(const uint64_t* keys, int64_t Ec, const pr_cold_params& prm, 
     GMX_REQUIRE(Ec < (1LL << 31) - (1LL << 27), "pr cold: %lld edges exceed the int32 stream positions", (long long) Ec);
     pr_cold* c = new pr_cold();
     c->prm = prm;
+    // the two tables are the caller's workspace memory and are read by this build alone (through `prm`): the plan keeps the
+    // scalars, not pointers that dangle once the caller's gmx_ws_scope has rewound
+    c->prm.index_of_row = nullptr;
+    c->prm.deg_by_id = nullptr;
     c->Ec = Ec;
     // GMX_PR_COLD_CLASS_DENSITY: 1 (default) = every tile in length classes (pair tiles by pair length, edge tiles as
     // class E1) with the larger tile that leaves; 0 = round 2's generic pair / edge forms; n > 1 = classes only for the
