@@ -1,4 +1,4 @@
-// gmx_tcd_plan.h -- the plan gmx_tcd.hip builds from the forward CSR, shared with gmx_lcc.hip (gmx_clustering) and gmx_ktruss.hip (gmx_ktruss).
+// gmx_tcd_plan.h -- the plan gmx_tcd.hip builds from the forward CSR, shared with gmx_lcc.hip (gmx_clustering), gmx_ktruss.hip (gmx_ktruss) and gmx_kclique.hip (gmx_kclique).
 #ifndef GMX_TCD_PLAN_H_
 #define GMX_TCD_PLAN_H_
 
@@ -26,6 +26,12 @@ struct tcd_plan {
     dbuf<int32_t> nb_idx;       // [2 E_up]
     dbuf<int32_t> nb_eid;       // [2 E_up]
     dbuf<int32_t> up_src;       // [E_up]: the row of edge id e in UP'
+    // gmx_kclique's additions, built on its first call on the plan (gmx_kclique.hip) and freed with it: the vertices listed by
+    // ascending d = |UP'(v)| (one device sort), and the offsets of the size classes in that list
+    bool kc_ready = false;
+    dbuf<int32_t> kc_vtx;           // [V]: plan ids by ascending d (ties: ascending id)
+    dbuf<int32_t> kc_d;             // [V]: their d
+    std::vector<int64_t> kc_below;  // [1026], host: kc_below[t] = vertices with d < t, so a class (lo, hi] is the list's [kc_below[lo + 1], kc_below[hi + 1])
 };
 
 // builds the plan of g (gmx_tcd.hip); the caller owns *out (gmx_tcd_plan_free)

@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_clustering, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_clustering, gmx_kclique, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge, gmx_v_cover's select and gmx_msf's weight and in_forest are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -832,6 +832,62 @@ int gmx_biconnected(gmx_graph_t* g, uint8_t* bridge_host, uint8_t* artic_host, i
  *   GMX_KTRUSS_PHASES      the device time of the plan additions, support, level scans, grid rounds, tail launches and finish, and the
  *                          largest number of decrements one edge received, on stderr (tools/ktruss_prof.py). */
 int gmx_ktruss(gmx_graph_t* g, int32_t* truss_host, int32_t* support_host, int32_t* max_truss, int64_t* num_edges, gmx_stats_t* stats);
+
+/* k-clique counting, in total and through every vertex, 3 <= k <= 8 (the reference has no such program).  The stored slots
+ * are read exactly as gmx_clustering and gmx_ktruss read them, N(v) = { u != v : v -> u or u -> v is stored }: self loops and
+ * repeated slots change nothing, rows may be in any order, and only the forward CSR is read (a GMX_GRAPH_NO_REVERSE graph
+ * works; there is no GMX_ERR_STATE).
+ * *cliques = the number of k-element vertex sets that are pairwise adjacent.  count_host[V] (int64, by the caller's vertex
+ * id) = the number of those sets that contain v, so that sum(count) == k * *cliques; k = 3 gives gmx_clustering's tri[] and
+ * triangles.  count_host may be NULL and is then neither built nor downloaded: the cheap total-only query, whose last level is
+ * a popcount and not an enumeration.  All sums are 64-bit and wrap modulo 2^64.  stats may be NULL.
+ * cliques == NULL, k outside 3 .. 8 or g == NULL (checked in this order, before g is touched): GMX_ERR_ARG before any device
+ * call.  V = 0: GMX_OK, nothing is written but *cliques = 0.  E = 0 or self loops only: GMX_OK, zeros, answered without a plan.
+ * When the plan's additions, the per-vertex scratch or the global class's matrices cannot be allocated: GMX_ERR_NOMEM, and the
+ * message gives the byte count.  Without the degree order an upper list whose bit matrix has 2^31 words or more (over 2^18
+ * entries) is GMX_ERR_ARG; the degree order keeps every list below 2^16 entries.
+ * Integers only: both results are unique and byte-identical from run to run and under every knob.
+ * Method:
+ *   plan     gmx_triangle_counting_directed's, gmx_clustering's and gmx_ktruss's, cached on the graph and shared with them
+ *            (whichever entry is called first builds it; GMX_KCLIQUE_NO_ORDER, GMX_KTRUSS_NO_ORDER, GMX_LCC_NO_ORDER and
+ *            GMX_TCD_NO_ORDER each rebuild a cached plan of the other order).  The first gmx_kclique call adds the vertices
+ *            listed by ascending d = |UP'(v)| (one device sort) and the offset of every d <= 1025 in that list, and frees
+ *            them with the plan.
+ *   matrix   for a plan vertex v with S = UP'(v) (ascending plan ids, local index = position in S), row i of the local bit
+ *            matrix is A[i] = { j > i : S_j in UP'(S_i) }: UP'(S_i) is streamed and searched in S.
+ *   count    a k-clique whose lowest plan id is v is a (k-1)-clique of that local DAG: P_1 = all; choose i_1, P_2 = A[i_1];
+ *            choose i_2 in P_2, P_3 = P_2 & A[i_2]; ... after k - 2 choices the last set is only popcounted.  Only the chosen
+ *            indices are kept; a word of P_t is the AND of at most six rows' words and is recomputed where it is read.
+ *   credits  a chosen index gets its subtree's total when the walk returns, the members of the last set +1 each into 64-bit
+ *            counters per local index, v the vertex total; the counters are flushed once per vertex to an array in plan ids,
+ *            which is permuted back on the device before the download.
+ *   classes  one launch each over a range of the list: wave (d <= 64: a word per row, a wave per vertex, a lane per i_1),
+ *            small (d <= min(256, cap)) and large (d <= cap): a workgroup per vertex with matrix, counters and list in
+ *            dynamic LDS (11 KiB; 140 KiB, one workgroup per CU), a wave per i_1 and a lane per i_2; global (d > cap): the
+ *            same with matrix and counters in workspace memory, one workgroup per vertex, dealt in batches; skipped
+ *            (d < k - 1): never launched.
+ * Every loop ends by construction and no kernel waits for a value that another workgroup writes.
+ * stats: iterations = 1, edges_examined = |UP'|, vertices_reached = the vertices with count > 0 (0 when count_host == NULL),
+ * kernel_ms = device time from the first launch after the plan to the last (the plan and its additions are graph
+ * preprocessing), d2h_ms = the downloads, h2d_ms = 0.
+ * Read at every call, no result byte depends on them:
+ *   GMX_KCLIQUE_NO_ORDER=1     the plan keeps the graph's numbering;
+ *   GMX_KCLIQUE_CAP            the large class's bound, default 1024, clamped to [64, 1024]: lowered, small graphs reach the
+ *                              global class;
+ *   GMX_KCLIQUE_WAVE=0         the wave class goes to the small class's kernel;
+ *   GMX_KCLIQUE_BATCH_BYTES    matrices and counters of one global-class launch, default 256 MiB (a vertex that needs more
+ *                              is a batch by itself);
+ *   GMX_KCLIQUE_PLAIN=1        every per-vertex credit as one global atomic, without the counters (the form they are measured
+ *                              against);
+ *   GMX_KCLIQUE_LOG=1          one line on stderr: `gmx kclique: plan V <V> E <E> up <|UP'|> order <degree|identity> built <0|1>
+ *                              classes_built <0|1>; k <k> cap <c> counts <lds|global|none>; items <a> wave + <b> small + <c> large
+ *                              + <d> global + <e> skipped; batches <n> cliques <C>`, a + b + c + d + e = V (no line when the
+ *                              call is answered without a plan);
+ *   GMX_KCLIQUE_PHASES         the device time of the plan additions, the matrices (every class launched once more, stopping
+ *                              behind its matrix), each class's count kernel less that share, and the finish, on stderr
+ *                              (tools/kclique_prof.py).  The extra launches lie inside the timed span: kernel_ms of such a
+ *                              call includes them, so take kernel_ms from calls without this knob. */
+int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64_t* cliques, gmx_stats_t* stats);
 
 /* The common-neighbour iterator, gm_common_neighbor_iter(G, s, d) (gm_common_neighbor_iter.cc:21-44): the slots of s's
  * row, in order and with their multiplicity, whose value occurs in d's row (Foreach(u: s.CommonNbrs(d)) <=>
