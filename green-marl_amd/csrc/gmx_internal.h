@@ -304,6 +304,8 @@ int gmx_keys_from_edges(const int32_t* src, const int32_t* dst, int64_t E, bool 
 // a[i] = i: the values a sort of keys carries along.  Defined in gmx_graph.hip and launched from gmx_route.hip as well: without
 // relocatable device code that works through the defining unit's host stub, so the kernel must stay non-static there.
 __global__ void iota_kernel(int32_t* __restrict__ a, int64_t n);
+// perm[order[j]] = j: the renumbering a sort by degree gives.  Defined in gmx_tc.hip and launched from gmx_tcd.hip as well, the same way.
+__global__ void tc_invert_kernel(const int32_t* __restrict__ order, int64_t V, int32_t* __restrict__ perm);
 
 // ---- cold-source part of the PageRank sweep (gmx_pr_cold.hip) ----
 // Sources whose id inside their rank range [r * slice, (r + 1) * slice) is >= T are "cold": their edges are not

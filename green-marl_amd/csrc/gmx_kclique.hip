@@ -29,7 +29,7 @@
 // Every loop ends by construction (a list, a row or a word range is walked once); no kernel waits for another workgroup.
 // Integers only: every result is unique and the same bytes under every knob.
 #include "gmx_tcd_plan.h"
-#include "gmx_tc_search.h"
+#include "gmx_rowgroup.h"
 #include "gmx_frontier.h"
 
 #include <rocprim/rocprim.hpp>
@@ -57,18 +57,9 @@
 
 typedef unsigned long long kc_word;
 
-enum { KC_TOTAL, KC_NONZERO, KC_SUM, KC_REAL, KC_NCTR };
+enum { KC_TOTAL, KC_NONZERO, KC_SUM, KC_NCTR };
 enum { KC_NONE = 0, KC_COUNTERS = 1, KC_PLAIN = 2 };   // MODE: where the per-vertex credits go
 enum { KC_SMALL, KC_LARGE, KC_GLOBAL };                // KIND of a workgroup kernel
-
-// first position in a[lo, hi) (ascending; LDS or memory) whose value is >= x
-__device__ __forceinline__ int32_t kc_lower_bound(const int32_t* a, int32_t lo, int32_t hi, int32_t x) {
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // the wave's sum, the same in every lane
 __device__ __forceinline__ kc_word kc_wave_total(kc_word x) {
@@ -183,15 +174,6 @@ __global__ void __launch_bounds__(KC_THREADS) kc_below_kernel(const int32_t* __r
     }
     below[t] = lo;
 }
-// forward slots that are no self loop (is there any edge at all: asked before a plan is built)
-__global__ void __launch_bounds__(KC_THREADS) kc_real_slots_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ idx, int64_t V, int64_t E,
-                                                                   kc_word* __restrict__ out) {
-    kc_word n = 0;
-    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < E; i += (int64_t) gridDim.x * blockDim.x)
-        n += idx[i] != csr_row_of(begin, V, (uint32_t) i) ? 1 : 0;
-    n = wave_sum(n);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(out, n);
-}
 
 // ------------------------------------------------------------------ wave class
 // list[0, n): vertices with k - 1 <= d <= 64.  A wave per vertex; lane i holds S_i, builds or shares in building row i and
@@ -221,9 +203,7 @@ __global__ void __launch_bounds__(KC_WAVES * 64) kc_wave_kernel(const int32_t* _
             be = up_begin[u + 1];
         }
         S[lane] = act ? u : INT32_MAX;
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_s_waitcnt(0xc07f);     // the wave's own LDS writes are visible to all its lanes
-        __builtin_amdgcn_wave_barrier();
+        rg_lds_landed();     // the wave's own LDS writes are visible to all its lanes
         const int32_t last = S[d - 1];
         // the matrix: a short UP'(S_i) by lane i alone, the others one after the other by the whole wave
         const bool by_wave = act && be - bb > alone_max;
@@ -232,13 +212,11 @@ __global__ void __launch_bounds__(KC_WAVES * 64) kc_wave_kernel(const int32_t* _
             for (int32_t p = bb; p < be; p++) {
                 const int32_t w = up_idx[p];
                 if (w > last) break;
-                const int32_t f = kc_lower_bound(S, lane + 1, d, w);
+                const int32_t f = rg_lower_bound<true>(S, lane + 1, d, w);
                 if (f < d && S[f] == w) row |= 1ull << f;
             }
         A[lane] = row;
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
+        rg_lds_landed();
         unsigned long long m = __ballot(by_wave);
         while (m) {   // (the same trip counts in every lane)
             const int src = __builtin_ctzll(m);
@@ -248,15 +226,13 @@ __global__ void __launch_bounds__(KC_WAVES * 64) kc_wave_kernel(const int32_t* _
                 const int32_t p = p0 + lane;
                 const int32_t w = p < sbe ? up_idx[p] : INT32_MAX;
                 if (w <= last) {
-                    const int32_t f = kc_lower_bound(S, src + 1, d, w);
+                    const int32_t f = rg_lower_bound<true>(S, src + 1, d, w);
                     if (f < d && S[f] == w) atomicOr(&A[src], 1ull << f);
                 }
                 if (__builtin_amdgcn_readfirstlane(w) > last) break;   // (lane 0 has p < sbe) sorted: nothing further is in S
             }
         }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_s_waitcnt(0xc07f);     // the wave's own LDS atomics have landed
-        __builtin_amdgcn_wave_barrier();
+        rg_lds_landed();     // the wave's own LDS atomics have landed
         if (!only_build) {
             kc_word mine = 0;
             if (act) {
@@ -268,9 +244,7 @@ __global__ void __launch_bounds__(KC_WAVES * 64) kc_wave_kernel(const int32_t* _
             if (MODE != KC_NONE) {
                 if (lane == 0 && tot) atomicAdd(&cnt[v], tot);
                 if (MODE == KC_COUNTERS) {   // flush the counters and leave them zero
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_s_waitcnt(0xc07f);
-                    __builtin_amdgcn_wave_barrier();
+                    rg_lds_landed();
                     const kc_word cv = c[lane];
                     if (cv) {   // (only a lane < d can hold credits)
                         c[lane] = 0;
@@ -330,7 +304,7 @@ __global__ void __launch_bounds__(KIND == KC_SMALL ? KC_SMALL_THREADS : KC_LARGE
                 const int32_t p = p0 + lane;
                 const int32_t w = p < be ? up_idx[p] : INT32_MAX;
                 if (w <= last) {
-                    const int32_t f = kc_lower_bound(S, i + 1, d, w);
+                    const int32_t f = rg_lower_bound<true>(S, i + 1, d, w);
                     if (f < d && S[f] == w) atomicOr(&A[i * W + (f >> 6)], 1ull << (f & 63));
                 }
                 if (__builtin_amdgcn_readfirstlane(w) > last) break;   // (lane 0 has p < be) sorted: nothing further is in S
@@ -499,7 +473,7 @@ extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64
     GMX_REQUIRE(g, "NULL graph");
     if (stats) memset(stats, 0, sizeof(*stats));
     *cliques = 0;
-    const int64_t V = g->V, E = g->E;
+    const int64_t V = g->V;
     if (V == 0) return GMX_OK;
     // knobs, read at every call; no result byte depends on them
     const bool ordered = !getenv("GMX_KCLIQUE_NO_ORDER");
@@ -510,19 +484,8 @@ extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64
     const bool phase_log = getenv("GMX_KCLIQUE_PHASES") != nullptr;
     const int mode = !count_host ? KC_NONE : plain ? KC_PLAIN : KC_COUNTERS;
     // E = 0 or self loops only: zeros, answered without a plan
-    dbuf<kc_word> out;
     int64_t real = 0;
-    if (g->tcd_cache) real = g->tcd_cache->E_up;
-    else if (E > 0) {
-        GMX_CHECK(out.alloc(KC_NCTR));
-        GMX_HIP(hipMemset(out.p, 0, KC_NCTR * sizeof(kc_word)));
-        hipLaunchKernelGGL(kc_real_slots_kernel, dim3(grid_for(E)), dim3(KC_THREADS), 0, 0, (const int32_t*) g->begin.p, (const int32_t*) g->node_idx.p, V, E,
-                           out.p + KC_REAL);
-        GMX_HIP(hipGetLastError());
-        kc_word h = 0;
-        GMX_HIP(hipMemcpy(&h, out.p + KC_REAL, sizeof(h), hipMemcpyDeviceToHost));
-        real = (int64_t) h;
-    }
+    GMX_CHECK(tcd_real_slots(g, &real));
     if (real == 0) {
         if (count_host) memset(count_host, 0, (size_t) V * sizeof(int64_t));
         if (stats) stats->iterations = 1;
@@ -530,15 +493,8 @@ extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64
     }
     // graph preprocessing (cached on the graph, shared with gmx_triangle_counting_directed, gmx_clustering and gmx_ktruss; outside the timed region)
     bool built = false;
-    if (g->tcd_cache && g->tcd_cache->ordered != ordered) {
-        gmx_tcd_plan_free(g->tcd_cache);
-        g->tcd_cache = nullptr;
-    }
-    if (!g->tcd_cache) {
-        GMX_CHECK(tcd_build_plan(g, ordered, &g->tcd_cache));
-        built = true;
-    }
-    tcd_plan* p = g->tcd_cache;
+    tcd_plan* p = nullptr;
+    GMX_CHECK(tcd_plan_get(g, ordered, &p, &built));
     float ph_ms[7] = {0, 0, 0, 0, 0, 0, 0};   // plan additions, matrices, wave, small, large, global, finish (GMX_KCLIQUE_PHASES)
     gmx_phase_clock phase;
     GMX_CHECK(phase.enable(phase_log));
@@ -573,11 +529,11 @@ extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64
     }
     // the call's scratch: cnt in the plan's numbering, the array asked for, the sums, the global class's workspace
     gmx_ws_scope scope;
-    dbuf<kc_word> cnt;
+    dbuf<kc_word> cnt, out;
     dbuf<int64_t> cnt_out;
     wbuf<kc_word> ws;
     const size_t scratch = (count_host ? 2 * (size_t) V * sizeof(int64_t) : 0) + KC_NCTR * sizeof(kc_word) + ws_bytes;
-    if ((!out.p && out.alloc(KC_NCTR)) || (count_host && (cnt.alloc((size_t) V) || cnt_out.alloc((size_t) V))) || (ws_bytes && ws.alloc(ws_bytes / sizeof(kc_word)))) {
+    if (out.alloc(KC_NCTR) || (count_host && (cnt.alloc((size_t) V) || cnt_out.alloc((size_t) V))) || (ws_bytes && ws.alloc(ws_bytes / sizeof(kc_word)))) {
         const std::string why = gmx_last_error();
         gmx_set_error("kclique: the per-vertex scratch and the global class's matrices need %zu bytes: %s", scratch, why.c_str());
         return GMX_ERR_NOMEM;

@@ -30,7 +30,7 @@
 //              hands back otherwise.
 // Rounds are separated by a kernel boundary or, in the tail, by a barrier.
 #include "gmx_tcd_plan.h"
-#include "gmx_tc_search.h"
+#include "gmx_rowgroup.h"
 #include "gmx_frontier.h"
 
 #include <rocprim/rocprim.hpp>
@@ -117,16 +117,6 @@ __global__ void __launch_bounds__(KT_THREADS) kt_fill_kernel(const uint32_t* __r
     }
 }
 
-// forward slots that are no self loop (is there any edge at all: asked before a plan is built)
-__global__ void __launch_bounds__(KT_THREADS) kt_real_slots_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ idx, int64_t V, int64_t E,
-                                                                   kt_word* __restrict__ out) {
-    kt_word n = 0;
-    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < E; i += (int64_t) gridDim.x * blockDim.x)
-        n += idx[i] != csr_row_of(begin, V, (uint32_t) i) ? 1 : 0;
-    n = wave_sum(n);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(out, n);
-}
-
 // ------------------------------------------------------------------ support
 // the shorter row of edge {a, b}, a < b (ties: a), as [*sb, *se), and the longer one as [*lb, *le)
 __device__ __forceinline__ void kt_rows(const int32_t* __restrict__ nb_begin, int32_t a, int32_t b, int32_t* sb, int32_t* se, int32_t* lb, int32_t* le) {
@@ -152,7 +142,7 @@ __global__ void __launch_bounds__(KT_THREADS) kt_support_kernel(const int32_t* _
         const bool by_wave = se - sb > lane_max;
         int32_t cnt = 0;
         if (!by_wave)
-            for (int32_t p = sb; p < se; p++) cnt += tc_contains(nb_idx, lb, le, nb_idx[p]) ? 1 : 0;
+            for (int32_t p = sb; p < se; p++) cnt += rg_contains<false>(nb_idx, lb, le, nb_idx[p]) ? 1 : 0;
         unsigned long long m = __ballot(by_wave);
         while (m) {   // the long rows, one after the other by the whole wave: the same trip counts in every lane
             const int src = __builtin_ctzll(m);
@@ -161,7 +151,7 @@ __global__ void __launch_bounds__(KT_THREADS) kt_support_kernel(const int32_t* _
             int32_t c = 0;
             for (int32_t p0 = wsb; p0 < wse; p0 += 64) {
                 const int32_t p = p0 + lane;
-                const bool hit = p < wse && tc_contains(nb_idx, wlb, wle, nb_idx[p]);
+                const bool hit = p < wse && rg_contains<false>(nb_idx, wlb, wle, nb_idx[p]);
                 c += (int32_t) __popcll(__ballot(hit));
             }
             if (lane == src) cnt = c;
@@ -243,7 +233,7 @@ __global__ void __launch_bounds__(KT_THREADS) kt_scan_kernel(kt_state S, const i
 __device__ __forceinline__ void kt_triangle(const kt_state& S, int32_t e, int32_t o, int32_t w, int32_t e1, int32_t round, int32_t* t1, int32_t* t2) {
     if (w == o) return;
     const int32_t ob = S.nb_begin[o], oe = S.nb_begin[o + 1];
-    const int32_t f = tc_lower_bound(S.nb_idx, ob, oe, w);
+    const int32_t f = rg_lower_bound<false>(S.nb_idx, ob, oe, w);
     if (f >= oe || S.nb_idx[f] != w) return;
     const int32_t e2 = S.nb_eid[f];
     const int32_t r1 = kt_load(&S.rem[e1]), r2 = kt_load(&S.rem[e2]);
@@ -465,7 +455,7 @@ __global__ void __launch_bounds__(KT_THREADS) kt_finish_kernel(const int32_t* __
         if (u != w) {
             const int32_t pu = perm ? perm[u] : u, pw = perm ? perm[w] : w;
             const int32_t a = pu < pw ? pu : pw, b = pu < pw ? pw : pu;
-            const int32_t e = tc_lower_bound(up_idx, up_begin[a], up_begin[a + 1], b);   // (there: {a, b} is an edge)
+            const int32_t e = rg_lower_bound<false>(up_idx, up_begin[a], up_begin[a + 1], b);   // (there: {a, b} is an edge)
             sv = sup0[e];
             if (truss_out) tv = truss[e];
         }
@@ -543,18 +533,7 @@ extern "C" int gmx_ktruss(gmx_graph_t* g, int32_t* truss_host, int32_t* support_
     const int64_t tail_from = gmx_env_int("GMX_KTRUSS_TAIL", KT_TAIL, 0, INT64_MAX);
     // E = 0 or self loops only: zero arrays, answered without a plan
     int64_t real = 0;
-    if (g->tcd_cache) real = g->tcd_cache->E_up;
-    else if (E > 0) {
-        dbuf<kt_word> cnt;
-        GMX_CHECK(cnt.alloc(1));
-        GMX_HIP(hipMemset(cnt.p, 0, sizeof(kt_word)));
-        hipLaunchKernelGGL(kt_real_slots_kernel, dim3(grid_for(E)), dim3(KT_THREADS), 0, 0, (const int32_t*) g->begin.p, (const int32_t*) g->node_idx.p, V, E,
-                           cnt.p);
-        GMX_HIP(hipGetLastError());
-        kt_word h = 0;
-        GMX_HIP(hipMemcpy(&h, cnt.p, sizeof(h), hipMemcpyDeviceToHost));
-        real = (int64_t) h;
-    }
+    GMX_CHECK(tcd_real_slots(g, &real));
     if (real == 0) {
         if (truss_host) memset(truss_host, 0, (size_t) E * sizeof(int32_t));
         if (support_host) memset(support_host, 0, (size_t) E * sizeof(int32_t));
@@ -562,15 +541,8 @@ extern "C" int gmx_ktruss(gmx_graph_t* g, int32_t* truss_host, int32_t* support_
     }
     // graph preprocessing (cached on the graph, shared with gmx_triangle_counting_directed and gmx_clustering; outside the timed region)
     bool built = false;
-    if (g->tcd_cache && g->tcd_cache->ordered != ordered) {
-        gmx_tcd_plan_free(g->tcd_cache);
-        g->tcd_cache = nullptr;
-    }
-    if (!g->tcd_cache) {
-        GMX_CHECK(tcd_build_plan(g, ordered, &g->tcd_cache));
-        built = true;
-    }
-    tcd_plan* p = g->tcd_cache;
+    tcd_plan* p = nullptr;
+    GMX_CHECK(tcd_plan_get(g, ordered, &p, &built));
     const int64_t U = p->E_up;
     if (num_edges) *num_edges = U;
     float ph_ms[6] = {0, 0, 0, 0, 0, 0};   // plan additions, support, level scans, grid rounds, finish, tail launches (GMX_KTRUSS_PHASES)

@@ -2,13 +2,13 @@
 //
 // The stored slots are read as an undirected simple graph: N(v) = { u != v : v -> u or u -> v is stored }, deg = |N|,
 //     tri[v] = #{ unordered {u, w} in N(v) : w in N(u) },   lcc[v] = 2 tri[v] / (deg[v] (deg[v] - 1)).
-// Plan: gmx_tcd.hip's (tcd_build_plan, cached on the graph and shared with gmx_triangle_counting_directed): perm, the
+// Plan: gmx_tcd.hip's (tcd_plan_get, cached on the graph and shared with gmx_triangle_counting_directed): perm, the
 // ascending-|N| renumbering, and UP', per vertex the distinct neighbours above it in that numbering, sorted.  Every
 // triangle is then found exactly once, as v < u < w with u, w in UP'(v) and w in UP'(u).  On top of the plan, on the first
 // call: the 64-slot groups of the UP' rows and UP' among the H highest ids as an H x H bit matrix (every upper neighbour of
 // one of them is one of them; with the degree order they are the hubs, as in gmx_tc.hip).
 //
-// Count: tc_oriented_kernel's walk (gmx_tc.hip) on UP'.  A work item is (v, group of 64 slots of UP'(v)), claimed from a
+// Count: tc_oriented_kernel's walk (gmx_tc.hip) on UP', on the work loop and the searches of gmx_rowgroup.h.  A work item is (v, group of 64 slots of UP'(v)), claimed from a
 // counter; UP'(v) from the group's first slot on is staged in the wave's LDS slice (at most `cap` entries; longer ones are
 // searched in memory).  Lane i owns the slot u = A[i]; its sides are the tail A(i, da) and UP'(u).  A side of at most `alone`
 // entries is walked by the lane itself; the other slots are taken one after the other by the whole wave, which probes the
@@ -30,9 +30,8 @@
 // Integers only: tri, deg, lcc (one IEEE division of two exact integers per vertex), triangles and wedges are exact and the
 // same bytes from run to run and under every knob.
 #include "gmx_tcd_plan.h"
-#include "gmx_tc_search.h"
-
-#include <rocprim/rocprim.hpp>
+#include "gmx_rowgroup.h"
+#include "gmx_frontier.h"
 
 #define LCC_THREADS 256
 #define LCC_WAVES 4
@@ -51,11 +50,6 @@ enum {
     LCC_NEXT, LCC_STAGED, LCC_MEMORY, LCC_SLOT_ALONE, LCC_SLOT_LIST, LCC_SLOT_TAIL, LCC_SLOT_HUB, LCC_SLOT_EMPTY, LCC_CREDIT_LDS,
     LCC_CREDIT_GLOBAL, LCC_SUM_TRI, LCC_WEDGES, LCC_NONZERO, LCC_NCTR
 };
-
-static int lcc_grid(int64_t n) {
-    const int64_t b = (n + LCC_THREADS - 1) / LCC_THREADS;
-    return (int) (b < 1 ? 1 : b > 256 * 16 ? 256 * 16 : b);
-}
 
 // ------------------------------------------------------------------ the hubs' bit matrix
 // One wave per hub row u = base + row: every w of UP'(u) is > u >= base, so it has a bit in the row.
@@ -87,17 +81,6 @@ __device__ __forceinline__ void lcc_credit_w(uint32_t* cnt, unsigned long long* 
     else atomicAdd(&tri[w], 1ull);
 }
 
-// lane 0's value, as one the compiler knows to be the same in every lane (scalar registers, scalar branches)
-__device__ __forceinline__ unsigned long long lcc_first_lane(unsigned long long x) {
-    return ((unsigned long long) (unsigned int) __builtin_amdgcn_readfirstlane((int) (x >> 32)) << 32) |
-           (unsigned int) __builtin_amdgcn_readfirstlane((int) x);
-}
-
-template <bool LDS>
-__device__ __forceinline__ int32_t lcc_lower_bound(const int32_t* R, int32_t lo, int32_t hi, int32_t x) {
-    return LDS ? tco_lds_lower_bound(R, lo, hi, x) : tc_lower_bound(R, lo, hi, x);
-}
-
 // One work item: R[0, da) is UP'(v) from the group's first slot on (LDS: the wave's slice; otherwise the row in memory), the
 // group's slots are R[0 .. 63], one per lane.  COUNTERS (only with LDS): the w credits go to cnt[], which is all zero on
 // entry and on return.  Returns the item's matches (the same in every lane).
@@ -125,6 +108,7 @@ __device__ __forceinline__ unsigned long long lcc_item(const int32_t* R, uint32_
     if (act && shorter > 0 && shorter <= alone_max) {
         if (tail_side && hubu) {
             const uint32_t* hrow = hub_bits + (int64_t) (u - hub_base) * hub_words;
+#pragma unroll 1   // (at most alone_max short steps: unrolled by four with a remainder, as the compiler does it inside rg_items' flat loop, GMX_LCC_PLAIN=1 was 0.4 % slower)
             for (int32_t p = lane + 1; p < da; p++) {
                 const int32_t w = R[p], wh = w - hub_base;   // w > u >= hub_base
                 if ((hrow[wh >> 5] >> (wh & 31)) & 1u) {
@@ -133,9 +117,10 @@ __device__ __forceinline__ unsigned long long lcc_item(const int32_t* R, uint32_
                 }
             }
         } else if (!tail_side) {
+#pragma unroll 1   // (as above: by two with a remainder otherwise)
             for (int32_t p = bb; p < be; p++) {
                 const int32_t w = up_idx[p];
-                const int32_t f = lcc_lower_bound<LDS>(R, lane + 1, da, w);
+                const int32_t f = rg_lower_bound<LDS>(R, lane + 1, da, w);
                 if (f < da && R[f] == w) {
                     cu++;
                     lcc_credit_w<COUNTERS>(cnt, tri, f, w);
@@ -144,7 +129,7 @@ __device__ __forceinline__ unsigned long long lcc_item(const int32_t* R, uint32_
         } else {
             for (int32_t p = lane + 1; p < da; p++) {
                 const int32_t w = R[p];
-                if (tc_contains(up_idx, bb, be, w)) {
+                if (rg_contains<false>(up_idx, bb, be, w)) {
                     cu++;
                     lcc_credit_w<COUNTERS>(cnt, tri, p, w);
                 }
@@ -187,7 +172,7 @@ __device__ __forceinline__ unsigned long long lcc_item(const int32_t* R, uint32_
                     if (p0 + 64 * k >= sbe) break;   // (the same in every lane)
                     bool hit = false;
                     if (w[k] >= 0) {
-                        const int32_t f = lcc_lower_bound<LDS>(R, src + 1, da, w[k]);
+                        const int32_t f = rg_lower_bound<LDS>(R, src + 1, da, w[k]);
                         hit = f < da && R[f] == w[k];
                         if (hit) lcc_credit_w<COUNTERS>(cnt, tri, f, w[k]);
                     }
@@ -201,7 +186,7 @@ __device__ __forceinline__ unsigned long long lcc_item(const int32_t* R, uint32_
                 bool hit = false;
                 if (p < da) {
                     const int32_t w = R[p];
-                    hit = tc_contains(up_idx, sbb, sbe, w);
+                    hit = rg_contains<false>(up_idx, sbb, sbe, w);
                     if (hit) lcc_credit_w<COUNTERS>(cnt, tri, p, w);
                 }
                 sc += (unsigned int) __popcll(__ballot(hit));
@@ -212,14 +197,12 @@ __device__ __forceinline__ unsigned long long lcc_item(const int32_t* R, uint32_
     unsigned long long tot = cu;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
-    tot = lcc_first_lane(tot);
+    tot = rg_first_lane(tot);
     if (lane == 0 && tot) atomicAdd(&tri[v], tot);
     if (COUNTERS) {
         // flush the positions' counters and leave them zero.  Lane i's first word holds position i, its own slot: u's credit
         // rides on that position's atomic
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_s_waitcnt(0xc07f);     // the wave's own LDS atomics have landed
-        __builtin_amdgcn_wave_barrier();
+        rg_lds_landed();
         if (tot) {
             unsigned int own = cu;              // (cu != 0: lane + 1 < da, so the loop below runs for k = lane)
             for (int32_t k = lane; k < da && k < LCC_CAP / 4; k += 64) {
@@ -257,44 +240,27 @@ lcc_count_kernel(const int32_t* __restrict__ up_begin, const int32_t* __restrict
         for (int k = lane; k < LCC_CAP / 4; k += 64) cnt[k] = 0;
         __builtin_amdgcn_wave_barrier();
     }
-    const int64_t Q = grp_off[V];
     lcc_tally t;
     unsigned int staged = 0, in_memory = 0;
     unsigned long long credit_lds = 0, credit_global = 0;
-    for (;;) {
-        unsigned long long b = 0;
-        if (lane == 0) b = atomicAdd(&ctr[LCC_NEXT], (unsigned long long) LCC_CLAIM);
-        b = lcc_first_lane(b);
-        if ((int64_t) b >= Q) break;
-        int64_t v = -1;
-        for (int64_t item = (int64_t) b; item < (int64_t) b + LCC_CLAIM && item < Q; item++) {
-            if (v < 0 || grp_off[v + 1] <= item) {   // vertex of the item: last v with grp_off[v] <= item
-                int64_t lo = 0, hi = V;
-                while (hi - lo > 1) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (grp_off[mid] <= item) lo = mid; else hi = mid;
-                }
-                v = lo;
-            }
-            const int32_t ab = up_begin[v] + (int32_t) (item - grp_off[v]) * 64, ae = up_begin[v + 1];
+    rg_items<LCC_CLAIM>(
+        grp_off, V, 0, 1, &ctr[LCC_NEXT], lane,
+        [&](int32_t v, int32_t group) {
+            const int32_t ab = up_begin[v] + group * 64, ae = up_begin[v + 1];
             const int32_t da = ae - ab;                 // UP'(v) from the group's first slot on (>= 2)
             if (da <= cap) {
-                for (int32_t k = lane; k < da; k += 64) A[k] = up_idx[ab + k];
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_s_waitcnt(0xc07f);     // the wave's own LDS writes are visible to all its lanes
-                __builtin_amdgcn_wave_barrier();
+                rg_stage(A, up_idx + ab, da, lane);
                 staged++;
-                const unsigned long long n = lcc_item<true, COUNTERS>(A, cnt, da, (int32_t) v, up_begin, up_idx, tri, hub_bits, hub_base, hub_words,
+                const unsigned long long n = lcc_item<true, COUNTERS>(A, cnt, da, v, up_begin, up_idx, tri, hub_bits, hub_base, hub_words,
                                                                       hub_tail, lane, alone_max, ratio, t);
                 if (COUNTERS) credit_lds += n; else credit_global += n;
-                __builtin_amdgcn_wave_barrier();        // all lanes are done with A before it is overwritten
+                rg_slice_done();
             } else {
                 in_memory++;
-                credit_global += lcc_item<false, false>(up_idx + ab, cnt, da, (int32_t) v, up_begin, up_idx, tri, hub_bits, hub_base, hub_words, hub_tail,
+                credit_global += lcc_item<false, false>(up_idx + ab, cnt, da, v, up_begin, up_idx, tri, hub_bits, hub_base, hub_words, hub_tail,
                                                         lane, alone_max, ratio, t);
             }
-        }
-    }
+        });
     if (lane == 0) {
         if (staged) atomicAdd(&ctr[LCC_STAGED], (unsigned long long) staged);
         if (in_memory) atomicAdd(&ctr[LCC_MEMORY], (unsigned long long) in_memory);
@@ -346,18 +312,7 @@ static int lcc_prepare(tcd_plan* p, int64_t H, bool* hub_built) {
     hipStream_t s = 0;
     const int64_t V = p->V;
     if (!p->lcc_ready) {
-        dbuf<int64_t> groups;
-        dbuf<char> tmp;
-        GMX_CHECK(groups.alloc((size_t) V + 1));
-        GMX_CHECK(p->up_grp_off.alloc((size_t) V + 1));
-        GMX_HIP(hipMemsetAsync(groups.p + V, 0, sizeof(int64_t), s));
-        hipLaunchKernelGGL(tcd_groups_kernel, dim3(lcc_grid(V)), dim3(LCC_THREADS), 0, s, (const int32_t*) p->up_begin.p, V, groups.p);
-        GMX_HIP(hipGetLastError());
-        size_t tb = 0;
-        GMX_HIP(rocprim::exclusive_scan(nullptr, tb, groups.p, p->up_grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), s));
-        GMX_CHECK(tmp.alloc(tb));
-        GMX_HIP(rocprim::exclusive_scan((void*) tmp.p, tb, groups.p, p->up_grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), s));
-        GMX_HIP(hipStreamSynchronize(s));
+        GMX_CHECK(tcd_group_offsets<dbuf>(p->up_begin.p, V, &p->up_grp_off, s));
         p->hubs = 0;
         p->lcc_ready = true;
     }
@@ -422,15 +377,8 @@ extern "C" int gmx_clustering(gmx_graph_t* g, int64_t* tri_host, int32_t* deg_ho
     if (!ordered) H = 0;
     // graph preprocessing (cached on the graph, shared with gmx_triangle_counting_directed; outside the timed region)
     bool built = false;
-    if (g->tcd_cache && g->tcd_cache->ordered != ordered) {
-        gmx_tcd_plan_free(g->tcd_cache);
-        g->tcd_cache = nullptr;
-    }
-    if (!g->tcd_cache) {
-        GMX_CHECK(tcd_build_plan(g, ordered, &g->tcd_cache));
-        built = true;
-    }
-    tcd_plan* p = g->tcd_cache;
+    tcd_plan* p = nullptr;
+    GMX_CHECK(tcd_plan_get(g, ordered, &p, &built));
     bool hub_built = false;
     GMX_CHECK(lcc_prepare(p, H, &hub_built));
     // the call's scratch: tri in the plan's numbering, the counters, the arrays asked for
@@ -459,7 +407,7 @@ extern "C" int gmx_clustering(gmx_graph_t* g, int64_t* tri_host, int32_t* deg_ho
         hipLaunchKernelGGL(lcc_count_kernel<true>, dim3(256 * 8), dim3(LCC_WAVES * 64), 0, 0, (const int32_t*) p->up_begin.p, (const int32_t*) p->up_idx.p,
                            (const int64_t*) p->up_grp_off.p, V, cap, alone, ratio, bits, hub_base, hub_words, hub_tail, tri.p, ctr.p);
     GMX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(lcc_finish_kernel, dim3(lcc_grid(V)), dim3(LCC_THREADS), 0, 0, (const unsigned long long*) tri.p, (const int32_t*) p->perm.p,
+    hipLaunchKernelGGL(lcc_finish_kernel, dim3(grid_for(V, LCC_THREADS, 256 * 16)), dim3(LCC_THREADS), 0, 0, (const unsigned long long*) tri.p, (const int32_t*) p->perm.p,
                        (const int32_t*) p->deg.p, V, tri_out.p, deg_out.p, lcc_out.p, ctr.p);
     GMX_HIP(hipGetLastError());
     GMX_CHECK(tm.end(tm.KERNEL));

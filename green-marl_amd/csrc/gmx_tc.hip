@@ -19,7 +19,8 @@
 // counted in its own numbering, as emitted.
 // Integer only: exact.
 #include "gmx_internal.h"
-#include "gmx_tc_search.h"
+#include "gmx_rowgroup.h"
+#include "gmx_frontier.h"
 
 #include <string.h>
 #include <rocprim/rocprim.hpp>
@@ -47,14 +48,14 @@ __device__ __forceinline__ unsigned long long tc_intersect(const int32_t* __rest
     if (tl <= rl) {
         // every tail slot (with multiplicity) that occurs in the in-row
         for (int32_t j = p.tb + lane; j < p.te; j += LANES)
-            c += tc_contains(r_node_idx, p.rb, p.re, node_idx[j]) ? 1 : 0;
+            c += rg_contains<false>(r_node_idx, p.rb, p.re, node_idx[j]) ? 1 : 0;
     } else {
         // every DISTINCT value of the in-row, times its multiplicity in the tail
         for (int32_t k = p.rb + lane; k < p.re; k += LANES) {
             int32_t x = r_node_idx[k];
             if (k > p.rb && r_node_idx[k - 1] == x) continue;
-            int32_t lo = tc_lower_bound(node_idx, p.tb, p.te, x);
-            int32_t hi = tc_lower_bound(node_idx, lo, p.te, x + 1);
+            int32_t lo = rg_lower_bound<false>(node_idx, p.tb, p.te, x);
+            int32_t hi = rg_lower_bound<false>(node_idx, lo, p.te, x + 1);
             c += (unsigned long long) (hi - lo);
         }
     }
@@ -83,10 +84,10 @@ tc_slots_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ n
         if (u <= v) continue;
         tc_pair p;
         p.te = begin[v + 1];
-        p.tb = tc_lower_bound(node_idx, (int32_t) e, p.te, u + 1);
+        p.tb = rg_lower_bound<false>(node_idx, (int32_t) e, p.te, u + 1);
         if (p.tb >= p.te) continue;
         p.re = r_begin[u + 1];
-        p.rb = tc_lower_bound(r_node_idx, r_begin[u], p.re, u + 1);
+        p.rb = rg_lower_bound<false>(r_node_idx, r_begin[u], p.re, u + 1);
         if (p.rb >= p.re) continue;
         const int32_t tl = p.te - p.tb, rl = p.re - p.rb;
         if ((tl < rl ? tl : rl) <= TC_SMALL) c += tc_intersect<1>(node_idx, r_node_idx, p, 0);
@@ -130,10 +131,10 @@ tc_forward_only_kernel(const int32_t* __restrict__ begin, const int32_t* __restr
         const int32_t v = (int32_t) lo, u = node_idx[e];
         if (u <= v) continue;
         const int32_t te = begin[v + 1];
-        const int32_t tb = tc_lower_bound(node_idx, (int32_t) e, te, u + 1);
+        const int32_t tb = rg_lower_bound<false>(node_idx, (int32_t) e, te, u + 1);
         for (int32_t j = tb + lane; j < te; j += 64) {
             const int32_t w = node_idx[j];
-            c += tc_contains(node_idx, begin[w], begin[w + 1], u) ? 1 : 0;   // w.HasEdgeTo(u)
+            c += rg_contains<false>(node_idx, begin[w], begin[w + 1], u) ? 1 : 0;   // w.HasEdgeTo(u)
         }
     }
 #pragma unroll
@@ -163,7 +164,7 @@ __global__ void tc_up_begin_kernel(const int32_t* __restrict__ begin, const int3
                                    int32_t* __restrict__ up_begin) {
     int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    for (; v < V; v += stride) up_begin[v] = tc_lower_bound(node_idx, begin[v], begin[v + 1], (int32_t) v + 1);
+    for (; v < V; v += stride) up_begin[v] = rg_lower_bound<false>(node_idx, begin[v], begin[v + 1], (int32_t) v + 1);
 }
 
 // The hubs' adjacency as bits.  On the degree-ordered copy the H highest ids are the H vertices of highest degree, and every
@@ -197,7 +198,8 @@ __global__ void tc_groups_kernel(const int32_t* __restrict__ begin, const int32_
 }
 
 // Work item = (vertex v, group g of 64 of its slots): a hub-like vertex (thousands of upper neighbours, each
-// with thousands of its own) is spread over many waves.  grp_off[V+1] = exclusive scan of the group counts.
+// with thousands of its own) is spread over many waves.  grp_off[V+1] = exclusive scan of the group counts.  The claim,
+// the item's vertex and the staging are gmx_rowgroup.h's; what is done with the group's slots is below.
 __global__ void __launch_bounds__(TCO_WAVES * 64)
 tc_oriented_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ node_idx, const int32_t* __restrict__ up_begin,
                    const int32_t* __restrict__ grp_off, int64_t V, int part, int nparts, int alone_max, int ratio,
@@ -207,35 +209,14 @@ tc_oriented_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict_
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
     int32_t* A = s_up[wv];
-    const int64_t G = grp_off[V];
-    const int64_t Q = G > part ? (G - part + nparts - 1) / nparts : 0;   // items part, part + nparts, ...
     unsigned long long c = 0;
-    for (;;) {
-        unsigned long long b = 0;
-        if (lane == 0) b = atomicAdd(next_claim, (unsigned long long) TCO_CLAIM);
-        b = __shfl(b, 0, 64);
-        if ((int64_t) b >= Q) break;
-        int64_t v = -1;
-        for (int64_t q = (int64_t) b; q < (int64_t) b + TCO_CLAIM && q < Q; q++) {
-            const int64_t item = q * nparts + part;
-            if (v < 0 || (int64_t) grp_off[v + 1] <= item) {   // vertex of the item: last v with grp_off[v] <= item
-                int64_t lo = 0, hi = V;
-                while (hi - lo > 1) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if ((int64_t) grp_off[mid] <= item) lo = mid; else hi = mid;
-                }
-                v = lo;
-            }
-            const int32_t base = (int32_t) (item - grp_off[v]) * 64;   // first slot of the group
-            const int32_t ab = up_begin[v] + base, ae = begin[v + 1];
+    rg_items<TCO_CLAIM>(
+        grp_off, V, part, nparts, next_claim, lane,
+        [&](int32_t v, int32_t group) {
+            const int32_t ab = up_begin[v] + group * 64 /* first slot of the group */, ae = begin[v + 1];
             const int32_t da = ae - ab;                                  // Up(v) from the group's first slot on
             const bool in_lds = da <= TCO_CAP;
-            if (in_lds) {
-                for (int32_t k = lane; k < da; k += 64) A[k] = node_idx[ab + k];
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_s_waitcnt(0xc07f);     // the wave's own LDS writes are visible to all its lanes
-                __builtin_amdgcn_wave_barrier();
-            }
+            if (in_lds) rg_stage(A, node_idx + ab, da, lane);
             // one slot per lane.  A lane whose shorter side is short walks it alone (probing the staged list or
             // Up(u)); the others are taken one after the other by the whole wave, lanes striding over the side
             // that is cheaper to stream.
@@ -263,14 +244,11 @@ tc_oriented_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict_
                 } else if (!tail_side) {
                     for (int32_t p = bb; p < be; p++) {
                         const int32_t w = node_idx[p];
-                        if (in_lds) {
-                            const int32_t f = tco_lds_lower_bound(A, i + 1, da, w);
-                            c += (f < da && A[f] == w) ? 1 : 0;
-                        } else c += tc_contains(node_idx, ab + i + 1, ae, w) ? 1 : 0;
+                        c += (in_lds ? rg_contains<true>(A, i + 1, da, w) : rg_contains<false>(node_idx, ab + i + 1, ae, w)) ? 1 : 0;
                     }
                 } else {
                     for (int32_t p = i + 1; p < da; p++)
-                        c += tc_contains(node_idx, bb, be, in_lds ? A[p] : node_idx[ab + p]) ? 1 : 0;
+                        c += rg_contains<false>(node_idx, bb, be, in_lds ? A[p] : node_idx[ab + p]) ? 1 : 0;
                 }
             }
             unsigned long long m = __ballot(act && shorter > alone_max);
@@ -305,18 +283,16 @@ tc_oriented_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict_
 #pragma unroll
                         for (int k = 0; k < TCO_PIECES; k++) {
                             if (w[k] < 0) continue;
-                            const int32_t f = tco_lds_lower_bound(A, src + 1, da, w[k]);
-                            c += (f < da && A[f] == w[k]) ? 1 : 0;
+                            c += rg_contains<true>(A, src + 1, da, w[k]) ? 1 : 0;
                         }
                     }
                 } else {                               // stream the tail of Up(v), search Up(u) in memory
                     for (int32_t p = src + 1 + lane; p < da; p += 64)
-                        c += tc_contains(node_idx, sbb, sbe, in_lds ? A[p] : node_idx[ab + p]) ? 1 : 0;
+                        c += rg_contains<false>(node_idx, sbb, sbe, in_lds ? A[p] : node_idx[ab + p]) ? 1 : 0;
                 }
             }
-            __builtin_amdgcn_wave_barrier();            // all lanes are done with A before it is overwritten
-        }
-    }
+            rg_slice_done();
+        });
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
     if (lane == 0 && c) atomicAdd(total, c);
@@ -330,11 +306,6 @@ tc_oriented_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict_
 static bool tc_use_lds() { return !getenv("GMX_TC_NO_LDS"); }
 
 // ------------------------------------------------------------------ degree-oriented copy
-static int tc_grid(int64_t n) {
-    int64_t b = (n + TC_THREADS - 1) / TC_THREADS;
-    return (int) (b < 1 ? 1 : b > 256 * 16 ? 256 * 16 : b);
-}
-
 // keys = (row << 32 | col) of the forward CSR, row-major: symmetric <=> both CSRs are the same arrays;
 // simple <=> no key with row == col and no two equal neighbours
 __global__ void tc_sym_check_kernel(const uint64_t* __restrict__ keys, const int32_t* __restrict__ node_idx,
@@ -383,7 +354,7 @@ static int tc_counting_graph(gmx_graph* g, gmx_graph** out, bool* oriented) {
         GMX_CHECK(bad.alloc(1));
         GMX_HIP(hipMemsetAsync(bad.p, 0, sizeof(int), s));
         GMX_CHECK(gmx_keys_from_csr(g->begin.p, g->node_idx.p, g->V, g->E, false, nullptr, keys.p, s));
-        hipLaunchKernelGGL(tc_sym_check_kernel, dim3(tc_grid(g->E > g->V ? g->E : g->V + 1)), dim3(TC_THREADS), 0, s,
+        hipLaunchKernelGGL(tc_sym_check_kernel, dim3(grid_for(g->E > g->V ? g->E : g->V + 1, TC_THREADS, 256 * 16)), dim3(TC_THREADS), 0, s,
                            (const uint64_t*) keys.p, g->node_idx.p, g->r_node_idx.p, g->begin.p, g->r_begin.p, g->V, g->E, bad.p);
         int hb = 1;
         GMX_HIP(hipMemcpy(&hb, bad.p, sizeof(int), hipMemcpyDeviceToHost));
@@ -396,13 +367,13 @@ static int tc_counting_graph(gmx_graph* g, gmx_graph** out, bool* oriented) {
             GMX_CHECK(id.alloc((size_t) g->V));
             GMX_CHECK(order.alloc((size_t) g->V));
             GMX_CHECK(perm.alloc((size_t) g->V));
-            hipLaunchKernelGGL(tc_degkey_kernel, dim3(tc_grid(g->V)), dim3(TC_THREADS), 0, s, g->begin.p, g->V, key.p, id.p);
+            hipLaunchKernelGGL(tc_degkey_kernel, dim3(grid_for(g->V, TC_THREADS, 256 * 16)), dim3(TC_THREADS), 0, s, g->begin.p, g->V, key.p, id.p);
             size_t tb = 0;
             GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, key.p, key2.p, id.p, order.p, (size_t) g->V, 0u, 32u, s));
             dbuf<char> tmp;
             GMX_CHECK(tmp.alloc(tb));
             GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, key.p, key2.p, id.p, order.p, (size_t) g->V, 0u, 32u, s));
-            hipLaunchKernelGGL(tc_invert_kernel, dim3(tc_grid(g->V)), dim3(TC_THREADS), 0, s, (const int32_t*) order.p, g->V, perm.p);
+            hipLaunchKernelGGL(tc_invert_kernel, dim3(grid_for(g->V, TC_THREADS, 256 * 16)), dim3(TC_THREADS), 0, s, (const int32_t*) order.p, g->V, perm.p);
             gmx_graph* o = new gmx_graph();
             o->V = g->V;
             o->E = g->E;
@@ -419,7 +390,7 @@ static int tc_counting_graph(gmx_graph* g, gmx_graph** out, bool* oriented) {
                 delete o;
                 return st;
             }
-            hipLaunchKernelGGL(tc_up_begin_kernel, dim3(tc_grid(g->V)), dim3(TC_THREADS), 0, s, o->begin.p, o->node_idx.p, g->V, o->r_begin.p);
+            hipLaunchKernelGGL(tc_up_begin_kernel, dim3(grid_for(g->V, TC_THREADS, 256 * 16)), dim3(TC_THREADS), 0, s, o->begin.p, o->node_idx.p, g->V, o->r_begin.p);
             // the hubs' adjacency as a bit matrix (GMX_TC_HUBS=<n> sets their number, 0 = none: development option)
             {
                 int64_t H = g->V > (1LL << 24) ? TCO_HUB_MAX : TCO_HUB_MAX / 2;   // (RMAT-24: 65536 and 131072 hubs measured the same, 32768 +30 %)
@@ -447,7 +418,7 @@ static int tc_counting_graph(gmx_graph* g, gmx_graph** out, bool* oriented) {
                     return st;
                 }
                 GMX_HIP(hipMemsetAsync(groups.p + g->V, 0, sizeof(int32_t), s));
-                hipLaunchKernelGGL(tc_groups_kernel, dim3(tc_grid(g->V)), dim3(TC_THREADS), 0, s, o->begin.p, (const int32_t*) o->r_begin.p, g->V, groups.p);
+                hipLaunchKernelGGL(tc_groups_kernel, dim3(grid_for(g->V, TC_THREADS, 256 * 16)), dim3(TC_THREADS), 0, s, o->begin.p, (const int32_t*) o->r_begin.p, g->V, groups.p);
                 size_t tb2 = 0;
                 GMX_HIP(rocprim::exclusive_scan(nullptr, tb2, groups.p, o->r_node_idx.p, 0, (size_t) g->V + 1, rocprim::plus<int32_t>(), s));
                 dbuf<char> tmp2;
@@ -578,7 +549,7 @@ common_nbr_count_kernel(const int32_t* __restrict__ begin, const int32_t* __rest
         const int32_t s = src[wave], d = dst[wave];
         const int32_t sb = begin[s], se = begin[s + 1], db = begin[d], de = begin[d + 1];
         unsigned long long c = 0;
-        for (int32_t j = sb + lane; j < se; j += 64) c += tc_contains(node_idx, db, de, node_idx[j]) ? 1 : 0;
+        for (int32_t j = sb + lane; j < se; j += 64) c += rg_contains<false>(node_idx, db, de, node_idx[j]) ? 1 : 0;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
         if (lane == 0) counts[wave] = (int64_t) c;
@@ -594,7 +565,7 @@ common_nbr_list_kernel(const int32_t* __restrict__ begin, const int32_t* __restr
     for (int32_t j0 = sb; j0 < se; j0 += 64) {
         const int32_t j = j0 + lane;
         const int32_t t = j < se ? node_idx[j] : 0;
-        const bool hit = j < se && tc_contains(node_idx, db, de, t);
+        const bool hit = j < se && rg_contains<false>(node_idx, db, de, t);
         const unsigned long long m = __ballot(hit);
         const int64_t at = n + __builtin_popcountll(m & ((1ull << lane) - 1));
         if (hit && at < cap) out[at] = t;
@@ -645,8 +616,8 @@ extern "C" int gmx_common_nbrs(gmx_graph_t* g, gmx_node_t s, gmx_node_t d, gmx_n
 // adamicAdar(G, aa) (apps/src/adamicAdar.gm; driver apps/output_cpp/src/adamicAdar_main.cc; the only application whose
 // emitted C++ uses gm_common_neighbor_iter): for every forward slot e = (from -> to)
 //     aa[e] = sum over the slots j of row(from), with multiplicity, whose value n occurs in row(to), of 1 / log(outdeg n).
-// Shaped like tc_oriented_kernel.  A work item is (vertex v, group of 64 of its slots); waves claim items from a counter,
-// stage row(v) in their LDS slice (once for all the groups of v inside a claim) and take the group's slots one per lane.
+// Shaped like tc_oriented_kernel, on the same work loop (gmx_rowgroup.h).  A work item is (vertex v, group of 64 of its slots); waves claim items from a
+// counter, stage row(v) in their LDS slice (once for all the groups of v they take in a row) and take the group's slots one per lane.
 // A slot whose shorter side is short is walked by its lane alone, the others by the whole wave one after the other: the
 // lanes stride over the shorter of row(from), row(to) and binary-search the longer; walking row(to) takes each distinct
 // value times its multiplicity in row(from), as tc_intersect does.  The lanes' partial sums are added in a fixed
@@ -678,7 +649,7 @@ __device__ __forceinline__ void aa_walk_from(const int32_t* R, int32_t da, const
                                              const double* __restrict__ w, int first, int step, double& sum, unsigned long long& k) {
     for (int32_t p = first; p < da; p += step) {
         const int32_t n = R[p];
-        if (tc_contains(node_idx, tb, te, n)) {
+        if (rg_contains<false>(node_idx, tb, te, n)) {
             sum += w[n];
             k++;
         }
@@ -691,11 +662,10 @@ __device__ __forceinline__ void aa_walk_to(const int32_t* R, int32_t da, const i
     for (int32_t p = tb + first; p < te; p += step) {
         const int32_t x = node_idx[p];
         if (p > tb && node_idx[p - 1] == x) continue;            // every distinct value of row(to) once
-        const int32_t lo = LDS ? tco_lds_lower_bound(R, 0, da, x) : tc_lower_bound(R, 0, da, x);
-        if (lo >= da || R[lo] != x) continue;
-        const int32_t hi = LDS ? tco_lds_lower_bound(R, lo + 1, da, x + 1) : tc_lower_bound(R, lo + 1, da, x + 1);
-        sum += (double) (hi - lo) * w[x];                          // ... times its multiplicity in row(from)
-        k += (unsigned long long) (hi - lo);
+        const int32_t n = rg_run<LDS>(R, 0, da, x);
+        if (n == 0) continue;
+        sum += (double) n * w[x];                                  // ... times its multiplicity in row(from)
+        k += (unsigned long long) n;
     }
 }
 
@@ -706,36 +676,21 @@ aa_rows_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ no
     __shared__ int32_t s_row[AA_WAVES][AA_CAP];
     const int lane = threadIdx.x & 63;
     int32_t* A = s_row[threadIdx.x >> 6];
-    const int64_t G = grp_off[V];
     unsigned long long nhit = 0;
-    for (;;) {
-        unsigned long long b = 0;
-        if (lane == 0) b = atomicAdd(next_claim, (unsigned long long) AA_CLAIM);
-        b = __shfl(b, 0, 64);
-        if ((int64_t) b >= G) break;
-        int64_t v = -1, staged = -1;
-        for (int64_t item = (int64_t) b; item < (int64_t) b + AA_CLAIM && item < G; item++) {
-            if (v < 0 || grp_off[v + 1] <= item) {   // vertex of the item: last v with grp_off[v] <= item
-                int64_t lo = 0, hi = V;
-                while (hi - lo > 1) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (grp_off[mid] <= item) lo = mid; else hi = mid;
-                }
-                v = lo;
-            }
+    int32_t staged = -1;   // the row in A: it stays there until the wave stages another one
+    rg_items<AA_CLAIM>(
+        grp_off, V, 0, 1, next_claim, lane,
+        [&](int32_t v, int32_t group) {
             const int32_t rb = begin[v], da = begin[v + 1] - rb;
             const int32_t* Rg = node_idx + rb;
             const bool in_lds = da <= cap;
-            if (in_lds && staged != v) {
-                __builtin_amdgcn_wave_barrier();            // all lanes are done with the row staged before
-                for (int32_t k = lane; k < da; k += 64) A[k] = Rg[k];
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_s_waitcnt(0xc07f);         // the wave's own LDS writes are visible to all its lanes
-                __builtin_amdgcn_wave_barrier();
+            if (in_lds && staged != v) {                    // the whole row is staged: once for all the groups of v
+                rg_slice_done();
+                rg_stage(A, Rg, da, lane);
                 staged = v;
             }
             // one slot per lane
-            const int32_t i = (int32_t) (item - grp_off[v]) * 64 + lane;
+            const int32_t i = group * 64 + lane;
             const bool act = i < da;
             const int32_t to = act ? (in_lds ? A[i] : Rg[i]) : -1;
             const int32_t before = __shfl_up(to, 1, 64);
@@ -792,8 +747,7 @@ aa_rows_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ no
                 aa[slot_of ? (int64_t) slot_of[e] : e] = sum;
                 nhit += k;
             }
-        }
-    }
+        });
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) nhit += __shfl_down(nhit, off, 64);
     if (lane == 0 && nhit) atomicAdd(hits, nhit);
@@ -827,7 +781,7 @@ extern "C" int gmx_adamic_adar(gmx_graph_t* g, double* aa_host, gmx_stats_t* sta
     GMX_CHECK(tm.begin(tm.KERNEL));
     GMX_HIP(hipMemsetAsync(ctr.p, 0, 2 * sizeof(unsigned long long), 0));
     GMX_HIP(hipMemsetAsync(groups.p + V, 0, sizeof(int64_t), 0));
-    hipLaunchKernelGGL(aa_weight_kernel, dim3(tc_grid(V)), dim3(TC_THREADS), 0, 0, (const int32_t*) g->begin.p, V, w.p, groups.p);
+    hipLaunchKernelGGL(aa_weight_kernel, dim3(grid_for(V, TC_THREADS, 256 * 16)), dim3(TC_THREADS), 0, 0, (const int32_t*) g->begin.p, V, w.p, groups.p);
     GMX_HIP(hipGetLastError());
     GMX_HIP(rocprim::exclusive_scan((void*) tmp.p, tb, groups.p, grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), 0));
     hipLaunchKernelGGL(aa_rows_kernel, dim3(256 * 8), dim3(AA_WAVES * 64), 0, 0, (const int32_t*) g->begin.p, (const int32_t*) g->node_idx.p,

@@ -10,14 +10,16 @@
 // not depend on the vertex numbering, and the count runs on a renumbered copy.
 //
 // Plan (graph preprocessing: built on first use from the forward CSR alone, cached on the graph, outside kernel_ms; the struct is
-// in gmx_tcd_plan.h because gmx_clustering, gmx_lcc.hip, shares the plan and keeps perm and |N(x)| with it):
+// in gmx_tcd_plan.h because gmx_clustering, gmx_ktruss and gmx_kclique share the plan and keep their additions with it; they get
+// it through tcd_plan_get, ask tcd_real_slots whether there is an edge at all, and scan their groups with tcd_group_offsets):
 //   N      the undirected simple neighbourhood: keys (s,d) and (d,s) of every slot with s != d, sorted, repeats dropped;
 //   perm   ascending |N(x)| (stable: ties by id), or the identity with GMX_TCD_NO_ORDER=1;
 //   OUT'   the forward rows renumbered and sorted, repeats and self loops kept (E entries);
 //   UP'    per vertex x the distinct y > x with adj(x, y), sorted (half of N's entries);
 //   groups exclusive scan of the 64-slot groups of the OUT' rows: a row of d >= 2 slots has ceil((d - 1) / 64) of them
 //          (its last slot has nothing above it).
-// Count: a work item is (v, group of 64 slots of OUT'(v)), claimed from a counter.  The row from the group's first slot on
+// Count: a work item is (v, group of 64 slots of OUT'(v)), claimed from a counter (the loop, the staging and the searches are
+// gmx_rowgroup.h's).  The row from the group's first slot on
 // is staged in the wave's LDS slice (at most `cap` entries; longer ones are searched in memory).  Lane i owns the slot
 // u = A[i]; its tail is A from the first position with a value > u (the run of equal values is skipped), the other side is
 // UP'(u).  With the degree order UP'(u) is short for a low-degree u and hubs own almost nothing.  A side of at most
@@ -28,7 +30,8 @@
 // slot adds one.  Both give the number of tail slots whose value is in UP'(u).
 // Integer only: exact.  64-bit partials per lane, a shuffle reduction, one atomic add per wave.
 #include "gmx_tcd_plan.h"
-#include "gmx_tc_search.h"
+#include "gmx_rowgroup.h"
+#include "gmx_frontier.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -49,11 +52,6 @@ enum { TCD_TOTAL, TCD_NEXT, TCD_STAGED, TCD_MEMORY, TCD_SLOT_ALONE, TCD_SLOT_LIS
 void gmx_tcd_plan_free(tcd_plan* p) { delete p; }
 
 // ------------------------------------------------------------------ plan kernels
-static int tcd_grid(int64_t n) {
-    const int64_t b = (n + TCD_THREADS - 1) / TCD_THREADS;
-    return (int) (b < 1 ? 1 : b > 256 * 16 ? 256 * 16 : b);
-}
-
 // both orientations of every slot that is no self loop; `none` (row V: sorts last) for the others
 __global__ void tcd_pair_keys_kernel(const uint64_t* __restrict__ fwd, int64_t E, uint64_t none, uint64_t* __restrict__ out) {
     int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -98,12 +96,6 @@ __global__ void tcd_degkey_kernel(const int32_t* __restrict__ nbegin, int64_t V,
     }
 }
 
-__global__ void tcd_invert_kernel(const int32_t* __restrict__ order, int64_t V, int32_t* __restrict__ perm) {
-    int64_t j = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
-    for (; j < V; j += stride) perm[order[j]] = (int32_t) j;
-}
-
 // the keys of N, renumbered (perm NULL: as they are): (x, y) with x < y stays, its mirror becomes `none`
 __global__ void tcd_up_keys_kernel(const uint64_t* __restrict__ nkeys, int64_t n, const int32_t* __restrict__ perm, uint64_t none,
                                    uint64_t* __restrict__ out) {
@@ -120,7 +112,8 @@ __global__ void tcd_up_keys_kernel(const uint64_t* __restrict__ nkeys, int64_t n
     }
 }
 
-__global__ void tcd_groups_kernel(const int32_t* __restrict__ begin, int64_t V, int64_t* __restrict__ groups) {
+// groups[v] = 64-slot groups of a row of d = begin[v + 1] - begin[v] slots: ceil((d - 1) / 64) from d = 2 on
+static __global__ void tcd_groups_kernel(const int32_t* __restrict__ begin, int64_t V, int64_t* __restrict__ groups) {
     int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t) gridDim.x * blockDim.x;
     for (; v < V; v += stride) {
@@ -129,21 +122,22 @@ __global__ void tcd_groups_kernel(const int32_t* __restrict__ begin, int64_t V, 
     }
 }
 
+// forward slots that are no self loop (is there any edge at all: asked before a plan is built)
+static __global__ void __launch_bounds__(TCD_THREADS) tcd_real_slots_kernel(const int32_t* __restrict__ begin, const int32_t* __restrict__ idx, int64_t V,
+                                                                            int64_t E, unsigned long long* __restrict__ out) {
+    unsigned long long n = 0;
+    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < E; i += (int64_t) gridDim.x * blockDim.x)
+        n += idx[i] != csr_row_of(begin, V, (uint32_t) i) ? 1 : 0;
+    n = wave_sum(n);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(out, n);
+}
+
 // ------------------------------------------------------------------ count kernel
 struct tcd_tally {   // what GMX_TCD_LOG reports: counted where the decisions are taken
     unsigned long long c = 0;          // per lane
     unsigned int alone = 0, empty = 0; // per lane
     unsigned int list = 0, tail = 0;   // per wave (the same in every lane)
 };
-
-// number of entries of R[lo, hi) equal to w (R non-decreasing)
-template <bool LDS>
-__device__ __forceinline__ int32_t tcd_run(const int32_t* R, int32_t lo, int32_t hi, int32_t w) {
-    const int32_t f = LDS ? tco_lds_lower_bound(R, lo, hi, w) : tc_lower_bound(R, lo, hi, w);
-    if (f >= hi || R[f] != w) return 0;
-    if (f + 1 >= hi || R[f + 1] != w) return 1;
-    return (LDS ? tco_lds_lower_bound(R, f + 2, hi, w + 1) : tc_lower_bound(R, f + 2, hi, w + 1)) - f;
-}
 
 // One work item: R[0, da) is OUT'(v) from the group's first slot on (the wave's LDS slice or the row in memory), the
 // group's slots are R[0 .. 63], one per lane; slot i pairs with the entries above its value.
@@ -154,7 +148,7 @@ __device__ __forceinline__ void tcd_item(const int32_t* R, int32_t da, const int
     int32_t bb = 0, be = 0, ts = da;
     if (act) {
         const int32_t u = R[lane];
-        ts = LDS ? tco_lds_lower_bound(R, lane + 1, da, u + 1) : tc_lower_bound(R, lane + 1, da, u + 1);
+        ts = rg_lower_bound<LDS>(R, lane + 1, da, u + 1);
         bb = up_begin[u];
         be = up_begin[u + 1];
     }
@@ -165,9 +159,9 @@ __device__ __forceinline__ void tcd_item(const int32_t* R, int32_t da, const int
     if (act && shorter > 0 && shorter <= alone_max) {
         t.alone++;
         if (tail_side) {
-            for (int32_t p = ts; p < da; p++) t.c += tc_contains(up_idx, bb, be, R[p]) ? 1 : 0;
+            for (int32_t p = ts; p < da; p++) t.c += rg_contains<false>(up_idx, bb, be, R[p]) ? 1 : 0;
         } else {
-            for (int32_t p = bb; p < be; p++) t.c += (unsigned long long) tcd_run<LDS>(R, ts, da, up_idx[p]);
+            for (int32_t p = bb; p < be; p++) t.c += (unsigned long long) rg_run<LDS>(R, ts, da, up_idx[p]);
         }
     }
     unsigned long long m = __ballot(act && shorter > alone_max);
@@ -185,12 +179,12 @@ __device__ __forceinline__ void tcd_item(const int32_t* R, int32_t da, const int
 #pragma unroll
                 for (int k = 0; k < TCD_PIECES; k++) {
                     if (w[k] < 0) continue;
-                    t.c += (unsigned long long) tcd_run<LDS>(R, sts, da, w[k]);
+                    t.c += (unsigned long long) rg_run<LDS>(R, sts, da, w[k]);
                 }
             }
         } else {                                             // stream the tail, search UP'(u) in memory
             t.tail++;
-            for (int32_t p = sts + lane; p < da; p += 64) t.c += tc_contains(up_idx, sbb, sbe, R[p]) ? 1 : 0;
+            for (int32_t p = sts + lane; p < da; p += 64) t.c += rg_contains<false>(up_idx, sbb, sbe, R[p]) ? 1 : 0;
         }
     }
 }
@@ -202,42 +196,23 @@ tcd_count_kernel(const int32_t* __restrict__ out_begin, const int32_t* __restric
     __shared__ int32_t s_row[TCD_WAVES][TCD_CAP];
     const int lane = threadIdx.x & 63;
     int32_t* A = s_row[threadIdx.x >> 6];
-    const int64_t G = grp_off[V];
-    const int64_t Q = G > part ? (G - part + nparts - 1) / nparts : 0;   // items part, part + nparts, ...
     tcd_tally t;
     unsigned int staged = 0, in_memory = 0;
-    for (;;) {
-        unsigned long long b = 0;
-        if (lane == 0) b = atomicAdd(&ctr[TCD_NEXT], (unsigned long long) TCD_CLAIM);
-        b = __shfl(b, 0, 64);
-        if ((int64_t) b >= Q) break;
-        int64_t v = -1;
-        for (int64_t q = (int64_t) b; q < (int64_t) b + TCD_CLAIM && q < Q; q++) {
-            const int64_t item = q * nparts + part;
-            if (v < 0 || grp_off[v + 1] <= item) {   // vertex of the item: last v with grp_off[v] <= item
-                int64_t lo = 0, hi = V;
-                while (hi - lo > 1) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (grp_off[mid] <= item) lo = mid; else hi = mid;
-                }
-                v = lo;
-            }
-            const int32_t ab = out_begin[v] + (int32_t) (item - grp_off[v]) * 64, ae = out_begin[v + 1];
+    rg_items<TCD_CLAIM>(
+        grp_off, V, part, nparts, &ctr[TCD_NEXT], lane,
+        [&](int32_t v, int32_t group) {
+            const int32_t ab = out_begin[v] + group * 64, ae = out_begin[v + 1];
             const int32_t da = ae - ab;                 // OUT'(v) from the group's first slot on (>= 2)
             if (da <= cap) {
-                for (int32_t k = lane; k < da; k += 64) A[k] = out_idx[ab + k];
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_s_waitcnt(0xc07f);     // the wave's own LDS writes are visible to all its lanes
-                __builtin_amdgcn_wave_barrier();
+                rg_stage(A, out_idx + ab, da, lane);
                 staged++;
                 tcd_item<true>(A, da, up_begin, up_idx, lane, alone_max, ratio, t);
-                __builtin_amdgcn_wave_barrier();        // all lanes are done with A before it is overwritten
+                rg_slice_done();
             } else {
                 in_memory++;
                 tcd_item<false>(out_idx + ab, da, up_begin, up_idx, lane, alone_max, ratio, t);
             }
-        }
-    }
+        });
     unsigned long long c = t.c, na = t.alone, ne = t.empty;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -274,7 +249,28 @@ static int tcd_sort_keys(uint64_t* a, uint64_t* b, int64_t n, unsigned end_bit, 
     return GMX_OK;
 }
 
-int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
+template <template <typename> class Buf>
+int tcd_group_offsets(const int32_t* begin, int64_t V, dbuf<int64_t>* grp_off, hipStream_t s) {
+    Buf<int64_t> groups;
+    Buf<char> tmp;
+    GMX_CHECK(groups.alloc((size_t) V + 1));
+    GMX_CHECK(grp_off->alloc((size_t) V + 1));
+    GMX_HIP(hipMemsetAsync(groups.p + V, 0, sizeof(int64_t), s));
+    hipLaunchKernelGGL(tcd_groups_kernel, dim3(grid_for(V, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, begin, V, groups.p);
+    GMX_HIP(hipGetLastError());
+    size_t tb = 0;
+    GMX_HIP(rocprim::exclusive_scan(nullptr, tb, groups.p, grp_off->p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), s));
+    GMX_CHECK(tmp.alloc(tb));
+    GMX_HIP(rocprim::exclusive_scan((void*) tmp.p, tb, groups.p, grp_off->p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), s));
+    GMX_HIP(hipStreamSynchronize(s));
+    return GMX_OK;
+}
+// the two forms the header promises: both are instantiated here, whoever calls them
+template int tcd_group_offsets<wbuf>(const int32_t*, int64_t, dbuf<int64_t>*, hipStream_t);   // tcd_build_plan below
+template int tcd_group_offsets<dbuf>(const int32_t*, int64_t, dbuf<int64_t>*, hipStream_t);   // gmx_lcc.hip's lcc_prepare
+
+// builds the plan of g; the caller owns *out (gmx_tcd_plan_free)
+static int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
     const int64_t V = g->V, E = g->E;
     hipStream_t s = 0;
     gmx_tick tick("tcd plan");
@@ -301,7 +297,7 @@ int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
     const unsigned end_bit = 32 + (unsigned) gmx_bits_for(V + 1);
     // N: both orientations, sorted, repeats dropped
     GMX_CHECK(gmx_keys_from_csr(g->begin.p, g->node_idx.p, V, E, false, nullptr, kb.p, s));
-    hipLaunchKernelGGL(tcd_pair_keys_kernel, dim3(tcd_grid(E)), dim3(TCD_THREADS), 0, s, (const uint64_t*) kb.p, E, none, ka.p);
+    hipLaunchKernelGGL(tcd_pair_keys_kernel, dim3(grid_for(E, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, (const uint64_t*) kb.p, E, none, ka.p);
     GMX_HIP(hipGetLastError());
     uint64_t *cur = nullptr, *oth = nullptr;
     GMX_CHECK(tcd_sort_keys(ka.p, kb.p, 2 * E, end_bit, s, &cur, &oth));
@@ -336,16 +332,16 @@ int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
             GMX_CHECK(key2.alloc((size_t) V));
             GMX_CHECK(perm.alloc((size_t) V));
         }
-        hipLaunchKernelGGL(tcd_extract_kernel, dim3(tcd_grid(V + 1)), dim3(TCD_THREADS), 0, s, (const uint64_t*) nkeys, V, n, (int64_t) 0, nbegin.p,
+        hipLaunchKernelGGL(tcd_extract_kernel, dim3(grid_for(V + 1, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, (const uint64_t*) nkeys, V, n, (int64_t) 0, nbegin.p,
                            (int32_t*) nullptr);
-        hipLaunchKernelGGL(tcd_degkey_kernel, dim3(tcd_grid(V)), dim3(TCD_THREADS), 0, s, (const int32_t*) nbegin.p, V, key.p, id.p, p->deg.p);
+        hipLaunchKernelGGL(tcd_degkey_kernel, dim3(grid_for(V, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, (const int32_t*) nbegin.p, V, key.p, id.p, p->deg.p);
         GMX_HIP(hipGetLastError());
         if (ordered) {
             size_t tb = 0;
             GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, key.p, key2.p, id.p, order.p, (size_t) V, 0u, 32u, s));
             GMX_CHECK(tmp.alloc(tb));
             GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, key.p, key2.p, id.p, order.p, (size_t) V, 0u, 32u, s));
-            hipLaunchKernelGGL(tcd_invert_kernel, dim3(tcd_grid(V)), dim3(TCD_THREADS), 0, s, (const int32_t*) order.p, V, perm.p);
+            hipLaunchKernelGGL(tc_invert_kernel, dim3(grid_for(V, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, (const int32_t*) order.p, V, perm.p);
             GMX_HIP(hipGetLastError());
         }
     }
@@ -355,12 +351,12 @@ int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
     GMX_CHECK(p->up_begin.alloc((size_t) V + 1));
     GMX_CHECK(p->up_idx.alloc((size_t) p->E_up));
     if (n > 0) {
-        hipLaunchKernelGGL(tcd_up_keys_kernel, dim3(tcd_grid(n)), dim3(TCD_THREADS), 0, s, (const uint64_t*) nkeys, n, (const int32_t*) perm.p, none, cur);
+        hipLaunchKernelGGL(tcd_up_keys_kernel, dim3(grid_for(n, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, (const uint64_t*) nkeys, n, (const int32_t*) perm.p, none, cur);
         GMX_HIP(hipGetLastError());
     }
     uint64_t *up_sorted = nullptr, *up_free = nullptr;
     GMX_CHECK(tcd_sort_keys(cur, nkeys, n, end_bit, s, &up_sorted, &up_free));
-    hipLaunchKernelGGL(tcd_extract_kernel, dim3(tcd_grid(p->E_up > V ? p->E_up : V + 1)), dim3(TCD_THREADS), 0, s, (const uint64_t*) up_sorted, V, n,
+    hipLaunchKernelGGL(tcd_extract_kernel, dim3(grid_for(p->E_up > V ? p->E_up : V + 1, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, (const uint64_t*) up_sorted, V, n,
                        p->E_up, p->up_begin.p, p->up_idx.p);
     GMX_HIP(hipGetLastError());
     GMX_HIP(hipStreamSynchronize(s));
@@ -372,24 +368,42 @@ int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
     GMX_CHECK(gmx_csr_from_keys(ka.p, kb.p, V, E, p->out_begin.p, p->out_idx.p, s));
     tick.mark("OUT'");
     // the work items
-    {
-        wbuf<int64_t> groups;
-        wbuf<char> tmp;
-        GMX_CHECK(groups.alloc((size_t) V + 1));
-        GMX_CHECK(p->grp_off.alloc((size_t) V + 1));
-        GMX_HIP(hipMemsetAsync(groups.p + V, 0, sizeof(int64_t), s));
-        hipLaunchKernelGGL(tcd_groups_kernel, dim3(tcd_grid(V)), dim3(TCD_THREADS), 0, s, (const int32_t*) p->out_begin.p, V, groups.p);
-        GMX_HIP(hipGetLastError());
-        size_t tb = 0;
-        GMX_HIP(rocprim::exclusive_scan(nullptr, tb, groups.p, p->grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), s));
-        GMX_CHECK(tmp.alloc(tb));
-        GMX_HIP(rocprim::exclusive_scan((void*) tmp.p, tb, groups.p, p->grp_off.p, (int64_t) 0, (size_t) V + 1, rocprim::plus<int64_t>(), s));
-        GMX_HIP(hipStreamSynchronize(s));
-    }
+    GMX_CHECK(tcd_group_offsets<wbuf>(p->out_begin.p, V, &p->grp_off, s));
     tick.mark("groups");
     p->build_ms = (gmx_tick::now() - t0) * 1e3;
     gd.p = nullptr;
     *out = p;
+    return GMX_OK;
+}
+
+int tcd_plan_get(gmx_graph* g, bool ordered, tcd_plan** out, bool* built) {
+    *built = false;
+    if (g->tcd_cache && g->tcd_cache->ordered != ordered) {
+        gmx_tcd_plan_free(g->tcd_cache);
+        g->tcd_cache = nullptr;
+    }
+    if (!g->tcd_cache) {
+        GMX_CHECK(tcd_build_plan(g, ordered, &g->tcd_cache));
+        *built = true;
+    }
+    *out = g->tcd_cache;
+    return GMX_OK;
+}
+
+int tcd_real_slots(const gmx_graph* g, int64_t* real) {
+    *real = 0;
+    if (g->tcd_cache) *real = g->tcd_cache->E_up;
+    else if (g->E > 0) {
+        dbuf<unsigned long long> cnt;
+        GMX_CHECK(cnt.alloc(1));
+        GMX_HIP(hipMemset(cnt.p, 0, sizeof(unsigned long long)));
+        hipLaunchKernelGGL(tcd_real_slots_kernel, dim3(grid_for(g->E)), dim3(TCD_THREADS), 0, 0, (const int32_t*) g->begin.p, (const int32_t*) g->node_idx.p,
+                           g->V, g->E, cnt.p);
+        GMX_HIP(hipGetLastError());
+        unsigned long long h = 0;
+        GMX_HIP(hipMemcpy(&h, cnt.p, sizeof(h), hipMemcpyDeviceToHost));
+        *real = (int64_t) h;
+    }
     return GMX_OK;
 }
 
@@ -406,15 +420,8 @@ static int tcd_count_part(gmx_graph_t* g, int part, int nparts, int64_t* count, 
     const int ratio = (int) gmx_env_int("GMX_TCD_RATIO", TCD_RATIO, 0, INT32_MAX);
     // graph preprocessing (cached on the graph like the reverse CSR; outside the timed region)
     bool built = false;
-    if (g->tcd_cache && g->tcd_cache->ordered != ordered) {
-        gmx_tcd_plan_free(g->tcd_cache);
-        g->tcd_cache = nullptr;
-    }
-    if (!g->tcd_cache) {
-        GMX_CHECK(tcd_build_plan(g, ordered, &g->tcd_cache));
-        built = true;
-    }
-    const tcd_plan* p = g->tcd_cache;
+    tcd_plan* p = nullptr;
+    GMX_CHECK(tcd_plan_get(g, ordered, &p, &built));
     dbuf<unsigned long long> ctr;
     GMX_CHECK(ctr.alloc(TCD_NCTR));
     GMX_HIP(hipMemset(ctr.p, 0, TCD_NCTR * sizeof(unsigned long long)));

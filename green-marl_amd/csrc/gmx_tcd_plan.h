@@ -1,4 +1,5 @@
-// gmx_tcd_plan.h -- the plan gmx_tcd.hip builds from the forward CSR, shared with gmx_lcc.hip (gmx_clustering), gmx_ktruss.hip (gmx_ktruss) and gmx_kclique.hip (gmx_kclique).
+// gmx_tcd_plan.h -- the plan gmx_tcd.hip builds from the forward CSR and caches on the graph, and how gmx_lcc.hip (gmx_clustering),
+// gmx_ktruss.hip (gmx_ktruss) and gmx_kclique.hip (gmx_kclique) get at it: the lookup, the empty-graph probe, the group offsets.
 #ifndef GMX_TCD_PLAN_H_
 #define GMX_TCD_PLAN_H_
 
@@ -34,10 +35,16 @@ struct tcd_plan {
     std::vector<int64_t> kc_below;  // [1026], host: kc_below[t] = vertices with d < t, so a class (lo, hi] is the list's [kc_below[lo + 1], kc_below[hi + 1])
 };
 
-// builds the plan of g (gmx_tcd.hip); the caller owns *out (gmx_tcd_plan_free)
-int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out);
-// groups[v] = 64-slot groups of a row of begin[v + 1] - begin[v] slots: ceil((d - 1) / 64) from d = 2 on (defined in
-// gmx_tcd.hip and launched from gmx_lcc.hip too, through the defining unit's host stub like iota_kernel)
-__global__ void tcd_groups_kernel(const int32_t* __restrict__ begin, int64_t V, int64_t* __restrict__ groups);
+// All in gmx_tcd.hip:
+// *out = g's cached plan, built first if there is none or the cached one has the other order (*built: it was built by this call)
+int tcd_plan_get(gmx_graph* g, bool ordered, tcd_plan** out, bool* built);
+// *real = the forward slots of g that are no self loop when g has no plan yet (one kernel pass and a read-back), else the
+// plan's E_up: zero exactly when there is no edge at all, which an entry asks before it has a plan built
+int tcd_real_slots(const gmx_graph* g, int64_t* real);
+// grp_off[0 .. V] (allocated here) = exclusive scan of the rows' 64-slot groups, a row of d = begin[v + 1] - begin[v] >= 2
+// slots having ceil((d - 1) / 64); synchronises s.  Buf: where the temporaries come from, wbuf inside a workspace scope or
+// dbuf (defined in gmx_tcd.hip, which instantiates exactly these two explicitly: another Buf is a link error)
+template <template <typename> class Buf>
+int tcd_group_offsets(const int32_t* begin, int64_t V, dbuf<int64_t>* grp_off, hipStream_t s);
 
 #endif
