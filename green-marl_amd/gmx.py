@@ -55,7 +55,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_biconnected", "gmx_ktruss", "gmx_kclique", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_biconnected", "gmx_ktruss", "gmx_kclique", "gmx_louvain", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -152,6 +152,7 @@ def lib():
         L.gmx_biconnected.argtypes = [vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_ktruss.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_kclique.argtypes = [vp, i32, vp, C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_louvain.argtypes = [vp, vp, i32, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_bfs_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
         L.gmx_bfs_free.argtypes = [vp]
         L.gmx_bfs_start.argtypes = [vp, i32]
@@ -768,6 +769,25 @@ class Graph:
         n, st = C.c_int64(0), Stats()
         _ck(lib().gmx_kclique(self._h, int(k), c.ctypes.data if per_vertex else None, C.byref(n), C.byref(st)))
         return (c[:V] if per_vertex else None, int(n.value), st.as_dict())
+
+    def louvain(self, weight=None, max_levels=32, max_rounds=64):
+        """Louvain modularity communities of the stored slots read as undirected edges -- returns (comm[int32], num_comms,
+        num_levels, modularity, intra, stats).  weight[E] int32 >= 1 by uploaded forward edge slot, or None: all 1; a repeated
+        slot is another edge and a self loop counts twice on the diagonal.  comm is numbered as wcc() numbers components,
+        num_levels counts the levels that kept a move, modularity = Qnum / m2^2 from the exact 128-bit numerator and intra is
+        the weight inside the communities (both directions).  All decisions are integer: the result is byte-identical to the
+        one-thread schedule in gmx.h.  Forward CSR only, any row order (gmx.h: GMX_LOUVAIN_*)."""
+        w = None
+        if weight is not None:
+            w = _i32(weight)
+            if w.shape != (self.E,):
+                raise ValueError("weight must have one entry per edge slot")
+        V = self.V
+        c = np.zeros(max(V, 1), np.int32)
+        nc, nl, q, intra, st = C.c_int32(0), C.c_int32(0), C.c_double(0.0), C.c_int64(0), Stats()
+        _ck(lib().gmx_louvain(self._h, w.ctypes.data if w is not None and self.E else None, int(max_levels), int(max_rounds), c.ctypes.data,
+                              C.byref(nc), C.byref(nl), C.byref(q), C.byref(intra), C.byref(st)))
+        return c[:V], int(nc.value), int(nl.value), float(q.value), int(intra.value), st.as_dict()
 
 
 def closeness_of(far, reach, wasserman_faust=False):

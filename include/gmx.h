@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_clustering, gmx_kclique, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_clustering, gmx_kclique, gmx_louvain, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge, gmx_v_cover's select and gmx_msf's weight and in_forest are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -888,6 +888,58 @@ int gmx_ktruss(gmx_graph_t* g, int32_t* truss_host, int32_t* support_host, int32
  *                              (tools/kclique_prof.py).  The extra launches lie inside the timed span: kernel_ms of such a
  *                              call includes them, so take kernel_ms from calls without this knob. */
 int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64_t* cliques, gmx_stats_t* stats);
+
+/* Louvain modularity communities (the reference has no such program).  The graph is read as gmx_msf reads it: every stored
+ * forward slot u -> w of weight x is an undirected edge; weight_host[E] is int32 by UPLOADED forward slot, NULL = every weight
+ * is 1; only the forward CSR is read, rows in any order, and a repeated slot is another edge (its weights add).  The symmetric
+ * integer matrix A: a slot with u != w adds x to A[u][w] and to A[w][u], a self-loop slot adds 2x to A[u][u].  k[u] = the sum
+ * of row u of A, m2 = the sum of all k = 2 sum x.  A weight below 1 is GMX_ERR_ARG, found by a device pass before any other
+ * work.  Weights go up to 2^31 - 1 and E stays below the int32 limit, so m2 < 2^63; every product below is formed in signed
+ * 128-bit integers.  The form is closed under contraction (A'[C][D] = the sum of A[u][w] over u in C, w in D): level 0 is the
+ * contraction of the doubled slot list under the identity map, and every level runs the same code.
+ * One level, on n level vertices with comm[i] = i and tot[c] = k[c]: q = Qnum = m2 intra - sum_c tot[c]^2, intra = the sum of
+ * A[u][w] over the pairs with comm[u] == comm[w].  Round r = 0, 1, ... of the level is two half-rounds; vertex i belongs to
+ * half fmix32(uint32(i) ^ (uint32(r) * 0x9E3779B9u)) & 1 (gmx_communities' hash), half 0 first.  A half-round evaluates every
+ * vertex of its half against ONE snapshot of comm and tot: with c = comm[i], e[D] = the sum of A[i][w] over w != i with
+ * comm[w] == D (e[c] exists even when it is 0) and score(D) = m2 e[D] - k[i] (tot[D] - (D == c ? k[i] : 0)), i keeps c when
+ * score(c) is the maximum over the keys of e, otherwise it takes the SMALLEST D with the maximum score.  All moves of the
+ * half-round are applied together (comm[i] = D, tot[c] -= k[i], tot[D] += k[i]) and Qnum is evaluated exactly: if something
+ * moved and the new Qnum is not strictly greater than q, the half-round is rolled back (comm, tot and q as before); otherwise
+ * q takes the new value.  A round that keeps no move ends the level, and so do max_rounds rounds, kept or not.  The level's
+ * non-empty labels are renumbered in ascending label order and the next level is the contraction.  A level that kept no move
+ * ends the run, and so does reaching max_levels levels.
+ * comm_host[V] = for each original vertex the community it lies in after the last level that kept a move, numbered as gmx_wcc
+ * numbers components (by ascending smallest member); *num_comms; *num_levels = the levels that kept a move; *intra = the final
+ * intra; *modularity = (double) Qnum / ((double) m2 * (double) m2): one correctly rounded conversion of the 128-bit numerator,
+ * one multiply, one divide, on the host; 0.0 when m2 == 0.  max_levels == 0 gives the identity and the singletons' modularity.
+ * GMX_ERR_ARG before g is touched otherwise: g == NULL, comm_host == NULL with V > 0, max_levels < 0, max_rounds < 1.  V = 0 or
+ * E = 0: GMX_OK, identity labels.  Every other out-pointer and stats may be NULL.  Nothing is cached on the graph.
+ * Integers only: the partition and the modularity are byte-identical to a one-thread run of this schedule, from run to run,
+ * under every knob and upload form.
+ * Method: per half-round the rows of the half are evaluated in three row-length regimes (short: 16 lanes per
+ * row, labels and weights in registers; wave: an open-addressing table label -> 64-bit sum in the wave's LDS slice; block: the
+ * same table in the workgroup's LDS; rows whose table fills: passes over disjoint label classes, any row length and label
+ * count), every table entry is scored with tot[D] gathered from the snapshot and the 128-bit (score, smaller label) maximum is
+ * reduced; moves go to a pending list (i, old, new); commit applies them with 64-bit atomics on tot; one sweep of the entries
+ * gives intra and a 128-bit reduction sum tot^2; a one-wave judge keeps or sets the roll-back flag, which the undo kernel
+ * obeys; the host reads one record per round.  Contraction: keys (comm[u] << 32 | comm[w]), a device sort, a reduce-by-key of
+ * the weights, row offsets and k; the level maps are composed on the device and gmx_wcc's scan gives the final numbering.
+ * Every loop ends by construction and no kernel waits for a value that another workgroup writes.
+ * stats: iterations = the rounds that kept a move, over all levels; vertices_reached = *num_comms; edges_examined = the sum
+ * over the levels of (rounds run, the last empty or rolled-back one included) x (entries of the level's merged adjacency,
+ * diagonal included); h2d_ms = the weights, kernel_ms = first launch to last, d2h_ms = the downloads.
+ * Read at every call, no result byte and no stat depends on them:
+ *   GMX_LOUVAIN_WAVE_MIN     rows of fewer entries are short; default 33, clamped to [1, 33] (a short row lies in registers);
+ *   GMX_LOUVAIN_BLOCK_MIN    rows of this many entries or more get a workgroup; default 256, at least 1;
+ *   GMX_LOUVAIN_LDS_SLOTS    the workgroup's table, default 4096, the power of two at or below the value clamped to
+ *                            [512, 8192]; a wave's table has an eighth of it;
+ *   GMX_LOUVAIN_LOG=1        one line on stderr: `gmx louvain: V <V> E <E> weighted <0|1> levels <l> rounds <rounds run> rollbacks
+ *                            <n> cuts <levels ended by max_rounds> moves <moves kept> sizes <n/nnz of every level run, or -> comms
+ *                            <c> intra <i> overflowed <rows sent to the class passes>` (no line for V = 0 or E = 0);
+ *   GMX_LOUVAIN_PHASES       per level the contraction's device time, per round the time of its evaluate and of its
+ *                            commit-measure-judge-undo launches, on stderr (tools/louvain_prof.py).  It synchronises. */
+int gmx_louvain(gmx_graph_t* g, const int32_t* weight_host, int32_t max_levels, int32_t max_rounds, gmx_node_t* comm_host, int32_t* num_comms,
+                int32_t* num_levels, double* modularity, int64_t* intra, gmx_stats_t* stats);
 
 /* The common-neighbour iterator, gm_common_neighbor_iter(G, s, d) (gm_common_neighbor_iter.cc:21-44): the slots of s's
  * row, in order and with their multiplicity, whose value occurs in d's row (Foreach(u: s.CommonNbrs(d)) <=>
