@@ -465,8 +465,8 @@ __global__ void __launch_bounds__(KT_THREADS) kt_finish_kernel(const int32_t* __
 }
 
 // ------------------------------------------------------------------ host
-// the plan's additions, once per plan
-static int kt_prepare(tcd_plan* p) {
+// the plan's additions, once per plan (declared in gmx_tcd_plan.h: gmx_squares.hip walks the same adjacency)
+int tcd_plan_adjacency(tcd_plan* p) {
     if (p->kt_ready) return GMX_OK;
     const int64_t V = p->V, U = p->E_up;
     GMX_REQUIRE(2 * U <= INT32_MAX, "ktruss: %lld undirected edges: the symmetric adjacency needs 32-bit offsets", (long long) U);
@@ -550,7 +550,7 @@ extern "C" int gmx_ktruss(gmx_graph_t* g, int32_t* truss_host, int32_t* support_
     GMX_CHECK(phase.enable(phase_log));
     const bool adj_built = !p->kt_ready;
     phase.begin();
-    GMX_CHECK(kt_prepare(p));
+    GMX_CHECK(tcd_plan_adjacency(p));
     phase.end(&ph_ms[0]);
     if (!truss_host && !support_host) return GMX_OK;   // only *num_edges was asked for
 

@@ -1,5 +1,6 @@
 // gmx_tcd_plan.h -- the plan gmx_tcd.hip builds from the forward CSR and caches on the graph, and how gmx_lcc.hip (gmx_clustering),
-// gmx_ktruss.hip (gmx_ktruss) and gmx_kclique.hip (gmx_kclique) get at it: the lookup, the empty-graph probe, the group offsets.
+// gmx_ktruss.hip (gmx_ktruss), gmx_kclique.hip (gmx_kclique) and gmx_squares.hip (gmx_squares) get at it: the lookup, the
+// empty-graph probe, the group offsets, the symmetric adjacency.
 #ifndef GMX_TCD_PLAN_H_
 #define GMX_TCD_PLAN_H_
 
@@ -19,9 +20,9 @@ struct tcd_plan {
     int64_t hubs = 0;           // the `hubs` highest plan ids, a multiple of 64 ...
     dbuf<uint32_t> hub_bits;    // ... and UP' among them as a hubs x hubs bit matrix: row u - (V - hubs), bit w - (V - hubs)
     double hub_ms = 0;
-    // gmx_ktruss's additions, built on its first call on the plan (gmx_ktruss.hip) and freed with it: the symmetric adjacency
-    // in plan ids, row v = DOWN'(v) then UP'(v) (sorted as it stands), with the edge id -- the position in up_idx -- of
-    // every slot, and the lower end of every edge id
+    // the symmetric adjacency, built by the first gmx_ktruss or gmx_squares call on the plan (tcd_plan_adjacency, in
+    // gmx_ktruss.hip) and freed with it: in plan ids, row v = DOWN'(v) then UP'(v) (sorted as it stands), with the edge id --
+    // the position in up_idx -- of every slot, and the lower end of every edge id
     bool kt_ready = false;
     dbuf<int32_t> nb_begin;     // [V + 1]
     dbuf<int32_t> nb_idx;       // [2 E_up]
@@ -33,6 +34,14 @@ struct tcd_plan {
     dbuf<int32_t> kc_vtx;           // [V]: plan ids by ascending d (ties: ascending id)
     dbuf<int32_t> kc_d;             // [V]: their d
     std::vector<int64_t> kc_below;  // [1026], host: kc_below[t] = vertices with d < t, so a class (lo, hi] is the list's [kc_below[lo + 1], kc_below[hi + 1])
+    // gmx_squares's additions, built on its first call on the plan (gmx_squares.hip) and freed with it.  D(u) = |DOWN'(u)| is
+    // nb_begin[u + 1] - nb_begin[u] - |UP'(u)| and u's DOWN' slots are numbered from nb_begin[u] - up_begin[u]
+    bool sq_ready = false;
+    dbuf<int32_t> sq_excl;          // [E_up]: per DOWN' slot (u, v) the sum of |{ w in N'(v') : w < u }| over the slots v' in front of it in u's row
+    dbuf<uint32_t> sq_W;            // [V]: W(u), the sum over the whole row: the wedges of u
+    dbuf<int32_t> sq_vtx;           // [V]: plan ids by ascending key (ties: ascending id); key = 0 where D(u) < 2, else W(u) + 1
+    std::vector<uint32_t> sq_key;   // [V], host: their keys, where the class offsets of a call's thresholds are searched
+    int64_t sq_wedges = 0;          // the sum of W(u) over the vertices with D(u) >= 2
 };
 
 // All in gmx_tcd.hip:
@@ -41,6 +50,8 @@ int tcd_plan_get(gmx_graph* g, bool ordered, tcd_plan** out, bool* built);
 // *real = the forward slots of g that are no self loop when g has no plan yet (one kernel pass and a read-back), else the
 // plan's E_up: zero exactly when there is no edge at all, which an entry asks before it has a plan built
 int tcd_real_slots(const gmx_graph* g, int64_t* real);
+// In gmx_ktruss.hip: the plan's symmetric adjacency (nb_begin, nb_idx, nb_eid, up_src), built unless it is there (kt_ready)
+int tcd_plan_adjacency(tcd_plan* p);
 // grp_off[0 .. V] (allocated here) = exclusive scan of the rows' 64-slot groups, a row of d = begin[v + 1] - begin[v] >= 2
 // slots having ceil((d - 1) / 64); synchronises s.  Buf: where the temporaries come from, wbuf inside a workspace scope or
 // dbuf (defined in gmx_tcd.hip, which instantiates exactly these two explicitly: another Buf is a link error)

@@ -55,7 +55,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_biconnected", "gmx_ktruss", "gmx_kclique", "gmx_louvain", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_biconnected", "gmx_ktruss", "gmx_kclique", "gmx_squares", "gmx_louvain", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -152,6 +152,7 @@ def lib():
         L.gmx_biconnected.argtypes = [vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_ktruss.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_kclique.argtypes = [vp, i32, vp, C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_squares.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_louvain.argtypes = [vp, vp, i32, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_bfs_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
         L.gmx_bfs_free.argtypes = [vp]
@@ -768,6 +769,18 @@ class Graph:
         c = np.zeros(max(V, 1), np.int64) if per_vertex else None
         n, st = C.c_int64(0), Stats()
         _ck(lib().gmx_kclique(self._h, int(k), c.ctypes.data if per_vertex else None, C.byref(n), C.byref(st)))
+        return (c[:V] if per_vertex else None, int(n.value), st.as_dict())
+
+    def squares(self, per_vertex=True):
+        """4-cycle (square) counts of the stored slots read as an undirected simple graph -- returns (count[int64, V] or None,
+        squares, stats).  squares is the number of cycles a - b - c - d - a on four distinct vertices (chords allowed: K4 holds
+        three; on a bipartite graph its butterflies), count[v] the number of those through v: count.sum() == 4 * squares.
+        per_vertex=False is the cheap total-only query: count is None and is not built.  Exact while 2 * count[v] < 2^63.
+        stats["edges_examined"] is the number of wedges walked.  Forward CSR only, any row order (gmx.h: GMX_SQUARES_*)."""
+        V = self.V
+        c = np.zeros(max(V, 1), np.int64) if per_vertex else None
+        n, st = C.c_int64(0), Stats()
+        _ck(lib().gmx_squares(self._h, c.ctypes.data if per_vertex else None, C.byref(n), C.byref(st)))
         return (c[:V] if per_vertex else None, int(n.value), st.as_dict())
 
     def louvain(self, weight=None, max_levels=32, max_rounds=64):

@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_clustering, gmx_kclique, gmx_louvain, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_clustering, gmx_kclique, gmx_squares, gmx_louvain, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge, gmx_v_cover's select and gmx_msf's weight and in_forest are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -888,6 +888,71 @@ int gmx_ktruss(gmx_graph_t* g, int32_t* truss_host, int32_t* support_host, int32
  *                              (tools/kclique_prof.py).  The extra launches lie inside the timed span: kernel_ms of such a
  *                              call includes them, so take kernel_ms from calls without this knob. */
 int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64_t* cliques, gmx_stats_t* stats);
+
+/* 4-cycle (square) counting, in total and through every vertex (the reference has no such program).  The stored slots are
+ * read exactly as gmx_clustering, gmx_ktruss and gmx_kclique read them, N(v) = { u != v : v -> u or u -> v is stored }: self
+ * loops and repeated slots change nothing, rows may be in any order, and only the forward CSR is read (a
+ * GMX_GRAPH_NO_REVERSE graph works; there is no GMX_ERR_STATE).
+ * A square is a set of four distinct vertices {a, b, c, d} with the edges ab, bc, cd, da present, counted once per such cycle;
+ * chords are allowed: K4 holds three squares, on one vertex set.  On a bipartite graph these are its butterflies.
+ * *squares = the number of squares.  count_host[V] (int64, by the caller's vertex id) = the number of squares through v, so
+ * that sum(count) == 4 * *squares.  count_host may be NULL and is then neither built nor downloaded: the cheap total-only
+ * query, which walks the wedges once and scatters no credit.  Results are exact while 2 * count[v] < 2^63 for every v (the
+ * end-vertex credits are accumulated doubled); beyond that they are unspecified.  stats may be NULL.
+ * squares == NULL or g == NULL (checked in this order, before g is touched): GMX_ERR_ARG before any device call.  V = 0: GMX_OK,
+ * nothing is written but *squares = 0.  E = 0 or self loops only: GMX_OK, zeros, answered without a plan.  When the plan's
+ * additions, the per-vertex scratch or the global class's counters cannot be allocated: GMX_ERR_NOMEM, and the message gives
+ * the byte count.  A graph with 2^30 undirected edges or more is GMX_ERR_ARG (the symmetric adjacency has 32-bit offsets).
+ * Integers only: both results are unique and byte-identical from run to run and under every knob.
+ * Method:
+ *   plan     the one gmx_triangle_counting_directed, gmx_clustering, gmx_ktruss and gmx_kclique share, cached on the graph, with
+ *            the symmetric adjacency gmx_ktruss adds to it (row v = DOWN'(v) then UP'(v), sorted; whichever of the two entries
+ *            is called first builds it).  GMX_SQUARES_NO_ORDER and the other entries' NO_ORDER knobs each rebuild a cached plan
+ *            of the other order.  The first gmx_squares call adds, and frees with the plan: per slot (u, v) of DOWN' the prefix
+ *            length |{ w in N'(v) : w < u }| (one binary search; kept as running sums inside u's row), W(u) = their sum over
+ *            u's row = the wedges of u, D(u) = |DOWN'(u)| (read off the adjacency), and the vertices listed by ascending W
+ *            (one device sort, the vertices with D(u) < 2 in front), whose keys the host keeps to find the class offsets.
+ *   count    in plan ids every square has one highest vertex u; its opposite vertex w and both middle vertices are below u.
+ *            c_u(w) = |{ v in DOWN'(u) : w in N'(v) }| for w < u: the squares with top u and opposite w number C(c_u(w), 2).
+ *            Pass 1 walks the wedges u - v - w and adds 1 to the entry of w in a table keyed by w.  Without count_host the add
+ *            returns the count before: the c adds to one entry return 0, 1, ..., c - 1 in some order, which sum to C(c, 2),
+ *            and there is no second pass.
+ *   credits  pass 2 walks the same wedges with x = c_u(w) - 1: v takes x (summed over the slot's wedges first: one 64-bit
+ *            atomic per DOWN' slot), w and u take x into a doubled accumulator (u's share by one wave reduction), which is
+ *            halved at the end: the c wedges to w give (c - 1) each, 2 C(c, 2) together.  count = mid + end2 / 2, held in plan
+ *            ids and permuted back on the device before the download.  No result depends on the order of the adds.
+ *   classes  one launch each over a range of the list.  The routing rule is part of the contract:
+ *              skipped  D(u) < 2: never launched;
+ *              wave     live, WAVE_MAX > 0 and W(u) <= WAVE_MAX: a wave per vertex, an open-addressing table (key w, count) of
+ *                       at least 2 W(u) slots in the wave's LDS slice, LDS atomics;
+ *              block    live, not wave, W(u) <= LDS_SLOTS / 2: the same with a workgroup per vertex, the table in dynamic LDS;
+ *              global   the rest: u int32 counters per vertex in workspace memory, dealt in batches of at most BATCH_BYTES: the
+ *                       list is cut greedily, a batch's vertices each get as many counters (a multiple of 64) as its highest
+ *                       plan id needs, and a vertex that alone exceeds the budget is a batch by itself.  Per batch a counting,
+ *                       a crediting (not without count_host) and a zeroing step; zeroing walks the wedges again and stores 0.
+ *                       The vertices with W(u) > SPLIT, a suffix of the batch, run in a launch of their own in every step: u is
+ *                       cut into min(ceil(W / SPLIT), D, 1024) ranges of DOWN'(u) of about equal wedges, a workgroup each.
+ * Every loop ends by construction and no kernel waits for a value that another workgroup writes.
+ * stats: iterations = 1, edges_examined = the wedges walked = the sum of W(u) over the vertices with D(u) >= 2,
+ * vertices_reached = the vertices with count > 0 (0 when count_host == NULL), kernel_ms = device time from the first launch
+ * after the plan and its additions to the last, d2h_ms = the downloads, h2d_ms = 0.
+ * Read at every call, no result byte depends on them:
+ *   GMX_SQUARES_NO_ORDER=1     the plan keeps the graph's numbering;
+ *   GMX_SQUARES_WAVE_MAX       default 128, clamped to [0, 128]; 0: no wave class;
+ *   GMX_SQUARES_LDS_SLOTS      table slots (8 bytes each) of a block-class workgroup, default 4096, clamped to [64, 18432];
+ *   GMX_SQUARES_BATCH_BYTES    counters of one global-class batch, default 1 GiB;
+ *   GMX_SQUARES_SPLIT          default 4096, at least 1;
+ *   GMX_SQUARES_PLAIN=1        every credit, u's included, as one global atomic per wedge (the form the others are measured
+ *                              against);
+ *   GMX_SQUARES_LOG=1          one line on stderr: `gmx squares: plan V <V> E <E> up <|UP'|> order <degree|identity> built <0|1>
+ *                              adj_built <0|1> classes_built <0|1>; wave_max <n> lds_slots <n> split <n> batch_bytes <n> counts
+ *                              <lds|global|none>; items <a> wave + <b> block + <c> global (<s> split) + <e> skipped; wedges <n>
+ *                              batches <n> squares <n>`, the thresholds as in force, a + b + c + e = V (no line when the call is
+ *                              answered without a plan);
+ *   GMX_SQUARES_PHASES         the device time of the additions (the adjacency included when this call builds it), each class
+ *                              and the finish, on stderr (tools/squares_prof.py).  It synchronises between the classes: take
+ *                              kernel_ms from calls without this knob. */
+int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares, gmx_stats_t* stats);
 
 /* Louvain modularity communities (the reference has no such program).  The graph is read as gmx_msf reads it: every stored
  * forward slot u -> w of weight x is an undirected edge; weight_host[E] is int32 by UPLOADED forward slot, NULL = every weight
