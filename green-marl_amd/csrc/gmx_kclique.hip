@@ -28,13 +28,9 @@
 //   skipped  d < k - 1: never launched.
 // Every loop ends by construction (a list, a row or a word range is walked once); no kernel waits for another workgroup.
 // Integers only: every result is unique and the same bytes under every knob.
-#include "gmx_tcd_plan.h"
-#include "gmx_rowgroup.h"
-#include "gmx_frontier.h"
-
-#include <rocprim/rocprim.hpp>
-
-#include <algorithm>
+// The credit modes, the mode dispatch, the batches, the finishing kernel and the frame of the entry are gmx_classcount.h's,
+// shared with gmx_squares.hip.
+#include "gmx_classcount.h"
 
 #define KC_THREADS 256
 #define KC_WAVES 4               // waves of a wave-class workgroup
@@ -55,38 +51,29 @@
 #define KC_MAX_K 8
 #define KC_ROWS (KC_MAX_K - 2)   // chosen indices at most
 
-typedef unsigned long long kc_word;
-
 enum { KC_TOTAL, KC_NONZERO, KC_SUM, KC_NCTR };
-enum { KC_NONE = 0, KC_COUNTERS = 1, KC_PLAIN = 2 };   // MODE: where the per-vertex credits go
-enum { KC_SMALL, KC_LARGE, KC_GLOBAL };                // KIND of a workgroup kernel
+enum { KC_SMALL, KC_LARGE, KC_GLOBAL };   // KIND of a workgroup kernel
 
-// the wave's sum, the same in every lane
-__device__ __forceinline__ kc_word kc_wave_total(kc_word x) {
-    x = wave_sum(x);
-    return ((kc_word) (unsigned int) __builtin_amdgcn_readfirstlane((int) (x >> 32)) << 32) | (unsigned int) __builtin_amdgcn_readfirstlane((int) x);
-}
-
-// n credits for local index j
+// n credits for local index j (MODE: gmx_classcount.h's; CC_LOCAL: the counters ctr[])
 template <int MODE>
-__device__ __forceinline__ void kc_credit(kc_word* ctr, kc_word* __restrict__ cnt, const int32_t* S, int32_t j, kc_word n) {
-    if (MODE == KC_COUNTERS) atomicAdd(&ctr[j], n);
-    if (MODE == KC_PLAIN) atomicAdd(&cnt[S[j]], n);
+__device__ __forceinline__ void kc_credit(cc_word* ctr, cc_word* __restrict__ cnt, const int32_t* S, int32_t j, cc_word n) {
+    if (MODE == CC_LOCAL) atomicAdd(&ctr[j], n);
+    if (MODE == CC_PLAIN) atomicAdd(&cnt[S[j]], n);
 }
 
 // The walk below N chosen rows ro[0 .. N) (offsets into A), LEFT more indices to choose before the popcount; `from` = the
 // word of the last chosen index.  Returns the cliques found; the chosen indices and the last set's members are credited.
 template <int LEFT, int N, int MODE>
-__device__ __forceinline__ kc_word kc_walk(const kc_word* A, int32_t W, int32_t (&ro)[KC_ROWS], int32_t from, kc_word* ctr, kc_word* __restrict__ cnt,
+__device__ __forceinline__ cc_word kc_walk(const cc_word* A, int32_t W, int32_t (&ro)[KC_ROWS], int32_t from, cc_word* ctr, cc_word* __restrict__ cnt,
                                            const int32_t* S) {
-    kc_word total = 0;
+    cc_word total = 0;
     for (int32_t w = from; w < W; w++) {
-        kc_word x = A[ro[0] + w];
+        cc_word x = A[ro[0] + w];
 #pragma unroll
         for (int s = 1; s < N; s++) x &= A[ro[s] + w];
         if constexpr (LEFT == 0) {
-            total += (kc_word) __popcll(x);
-            if (MODE != KC_NONE)
+            total += (cc_word) __popcll(x);
+            if (MODE != CC_NONE)
                 while (x) {
                     const int32_t j = w * 64 + __builtin_ctzll(x);
                     x &= x - 1;
@@ -97,9 +84,9 @@ __device__ __forceinline__ kc_word kc_walk(const kc_word* A, int32_t W, int32_t 
                 const int32_t j = w * 64 + __builtin_ctzll(x);
                 x &= x - 1;
                 ro[N] = j * W;
-                const kc_word sub = kc_walk<LEFT - 1, N + 1, MODE>(A, W, ro, w, ctr, cnt, S);
+                const cc_word sub = kc_walk<LEFT - 1, N + 1, MODE>(A, W, ro, w, ctr, cnt, S);
                 total += sub;
-                if (MODE != KC_NONE && sub) kc_credit<MODE>(ctr, cnt, S, j, sub);
+                if (MODE != CC_NONE && sub) kc_credit<MODE>(ctr, cnt, S, j, sub);
             }
         }
     }
@@ -108,8 +95,8 @@ __device__ __forceinline__ kc_word kc_walk(const kc_word* A, int32_t W, int32_t 
 
 // the same with LEFT = left known at run time (N + left <= KC_ROWS: the caller's k <= 8)
 template <int N, int MODE>
-__device__ __forceinline__ kc_word kc_walk_from(int left, const kc_word* A, int32_t W, int32_t (&ro)[KC_ROWS], int32_t from, kc_word* ctr,
-                                                kc_word* __restrict__ cnt, const int32_t* S) {
+__device__ __forceinline__ cc_word kc_walk_from(int left, const cc_word* A, int32_t W, int32_t (&ro)[KC_ROWS], int32_t from, cc_word* ctr,
+                                                cc_word* __restrict__ cnt, const int32_t* S) {
     switch (left) {
     case 0: return kc_walk<0, N, MODE>(A, W, ro, from, ctr, cnt, S);
     case 1: return kc_walk<1, N, MODE>(A, W, ro, from, ctr, cnt, S);
@@ -125,10 +112,10 @@ __device__ __forceinline__ kc_word kc_walk_from(int left, const kc_word* A, int3
 // The same walk for rows of ONE word (the wave class): the candidate set itself, x = the AND of the chosen rows, goes down in
 // a register instead of the chosen rows, so a level costs one row read.  LEFT more indices to choose before x is popcounted.
 template <int LEFT, int MODE>
-__device__ __forceinline__ kc_word kc_walk_word(const kc_word* A, kc_word x, kc_word* ctr, kc_word* __restrict__ cnt, const int32_t* S) {
+__device__ __forceinline__ cc_word kc_walk_word(const cc_word* A, cc_word x, cc_word* ctr, cc_word* __restrict__ cnt, const int32_t* S) {
     if constexpr (LEFT == 0) {
-        const kc_word total = (kc_word) __popcll(x);
-        if (MODE != KC_NONE)
+        const cc_word total = (cc_word) __popcll(x);
+        if (MODE != CC_NONE)
             while (x) {
                 const int32_t j = __builtin_ctzll(x);
                 x &= x - 1;
@@ -136,19 +123,19 @@ __device__ __forceinline__ kc_word kc_walk_word(const kc_word* A, kc_word x, kc_
             }
         return total;
     } else {
-        kc_word total = 0;
+        cc_word total = 0;
         while (x) {
             const int32_t j = __builtin_ctzll(x);
             x &= x - 1;
-            const kc_word sub = kc_walk_word<LEFT - 1, MODE>(A, x & A[j], ctr, cnt, S);   // (row j holds bits above j only)
+            const cc_word sub = kc_walk_word<LEFT - 1, MODE>(A, x & A[j], ctr, cnt, S);   // (row j holds bits above j only)
             total += sub;
-            if (MODE != KC_NONE && sub) kc_credit<MODE>(ctr, cnt, S, j, sub);
+            if (MODE != CC_NONE && sub) kc_credit<MODE>(ctr, cnt, S, j, sub);
         }
         return total;
     }
 }
 template <int MODE>
-__device__ __forceinline__ kc_word kc_walk_word_from(int left, const kc_word* A, kc_word x, kc_word* ctr, kc_word* __restrict__ cnt, const int32_t* S) {
+__device__ __forceinline__ cc_word kc_walk_word_from(int left, const cc_word* A, cc_word x, cc_word* ctr, cc_word* __restrict__ cnt, const int32_t* S) {
     switch (left) {
     case 0: return kc_walk_word<0, MODE>(A, x, ctr, cnt, S);
     case 1: return kc_walk_word<1, MODE>(A, x, ctr, cnt, S);
@@ -181,16 +168,16 @@ __global__ void __launch_bounds__(KC_THREADS) kc_below_kernel(const int32_t* __r
 template <int MODE>
 __global__ void __launch_bounds__(KC_WAVES * 64) kc_wave_kernel(const int32_t* __restrict__ up_begin, const int32_t* __restrict__ up_idx,
                                                                 const int32_t* __restrict__ list, int64_t n, int k, int alone_max, int only_build,
-                                                                kc_word* __restrict__ cnt /* [V] by plan id, or NULL */, kc_word* __restrict__ out) {
-    __shared__ kc_word s_A[KC_WAVES][64];
-    __shared__ kc_word s_c[KC_WAVES][64];
+                                                                cc_word* __restrict__ cnt /* [V] by plan id, or NULL */, cc_word* __restrict__ out) {
+    __shared__ cc_word s_A[KC_WAVES][64];
+    __shared__ cc_word s_c[KC_WAVES][64];
     __shared__ int32_t s_S[KC_WAVES][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    kc_word* A = s_A[wv];
-    kc_word* c = s_c[wv];
+    cc_word* A = s_A[wv];
+    cc_word* c = s_c[wv];
     int32_t* S = s_S[wv];
     c[lane] = 0;
-    kc_word total = 0;
+    cc_word total = 0;
     const int64_t nwaves = (int64_t) gridDim.x * KC_WAVES;
     for (int64_t it = (int64_t) blockIdx.x * KC_WAVES + wv; it < n; it += nwaves) {   // (wave-uniform)
         const int32_t v = list[it];
@@ -207,7 +194,7 @@ __global__ void __launch_bounds__(KC_WAVES * 64) kc_wave_kernel(const int32_t* _
         const int32_t last = S[d - 1];
         // the matrix: a short UP'(S_i) by lane i alone, the others one after the other by the whole wave
         const bool by_wave = act && be - bb > alone_max;
-        kc_word row = 0;
+        cc_word row = 0;
         if (act && !by_wave)
             for (int32_t p = bb; p < be; p++) {
                 const int32_t w = up_idx[p];
@@ -234,18 +221,18 @@ __global__ void __launch_bounds__(KC_WAVES * 64) kc_wave_kernel(const int32_t* _
         }
         rg_lds_landed();     // the wave's own LDS atomics have landed
         if (!only_build) {
-            kc_word mine = 0;
+            cc_word mine = 0;
             if (act) {
                 mine = kc_walk_word_from<MODE>(k - 3, A, A[lane], c, cnt, S);
-                if (MODE != KC_NONE && mine) kc_credit<MODE>(c, cnt, S, lane, mine);
+                if (MODE != CC_NONE && mine) kc_credit<MODE>(c, cnt, S, lane, mine);
             }
-            const kc_word tot = kc_wave_total(mine);
+            const cc_word tot = cc_wave_total(mine);
             total += tot;
-            if (MODE != KC_NONE) {
+            if (MODE != CC_NONE) {
                 if (lane == 0 && tot) atomicAdd(&cnt[v], tot);
-                if (MODE == KC_COUNTERS) {   // flush the counters and leave them zero
+                if (MODE == CC_LOCAL) {   // flush the counters and leave them zero
                     rg_lds_landed();
-                    const kc_word cv = c[lane];
+                    const cc_word cv = c[lane];
                     if (cv) {   // (only a lane < d can hold credits)
                         c[lane] = 0;
                         atomicAdd(&cnt[u], cv);
@@ -260,7 +247,7 @@ __global__ void __launch_bounds__(KC_WAVES * 64) kc_wave_kernel(const int32_t* _
 
 // ------------------------------------------------------------------ small, large and global classes
 // dynamic LDS of a workgroup whose vertices have d <= dmax (a multiple of 64): matrix, counters, list
-static size_t kc_lds_bytes(int dmax) { return (size_t) dmax * (dmax >> 6) * sizeof(kc_word) + (size_t) dmax * sizeof(kc_word) + (size_t) dmax * sizeof(int32_t); }
+static size_t kc_lds_bytes(int dmax) { return (size_t) dmax * (dmax >> 6) * sizeof(cc_word) + (size_t) dmax * sizeof(cc_word) + (size_t) dmax * sizeof(int32_t); }
 // global class: 64-bit words of the matrix and the counters of a vertex of d upper neighbours, in whole 256-byte lines
 static int64_t kc_ws_words(int64_t d) { return (d * ((d + 63) >> 6) + d + 31) & ~(int64_t) 31; }
 
@@ -271,19 +258,19 @@ static int64_t kc_ws_words(int64_t d) { return (d * ((d + 63) >> 6) + d + 31) & 
 template <int MODE, int KIND>
 __global__ void __launch_bounds__(KIND == KC_SMALL ? KC_SMALL_THREADS : KC_LARGE_THREADS) kc_block_kernel(const int32_t* __restrict__ up_begin, const int32_t* __restrict__ up_idx,
                                                                     const int32_t* __restrict__ list, int64_t n, int split, int k, int dmax, int only_build,
-                                                                    kc_word* __restrict__ ws, int64_t ws_stride, kc_word* __restrict__ cnt,
-                                                                    kc_word* __restrict__ out) {
+                                                                    cc_word* __restrict__ ws, int64_t ws_stride, cc_word* __restrict__ cnt,
+                                                                    cc_word* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char kc_lds[];
     constexpr bool GLOBAL = KIND == KC_GLOBAL;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, T = blockDim.x, nwaves = T >> 6;
-    kc_word* A = GLOBAL ? nullptr : (kc_word*) kc_lds;
-    kc_word* c = GLOBAL ? nullptr : A + (size_t) dmax * (dmax >> 6);
+    cc_word* A = GLOBAL ? nullptr : (cc_word*) kc_lds;
+    cc_word* c = GLOBAL ? nullptr : A + (size_t) dmax * (dmax >> 6);
     int32_t* S_lds = GLOBAL ? nullptr : (int32_t*) (c + dmax);
     if (!GLOBAL) {
         for (int j = tid; j < dmax; j += T) c[j] = 0;
         __syncthreads();
     }
-    kc_word total = 0;
+    cc_word total = 0;
     for (int64_t it = blockIdx.x; it < n * split; it += gridDim.x) {   // (workgroup-uniform)
         const int32_t v = list[it / split], share = (int32_t) (it % split);
         const int32_t ab = up_begin[v], d = up_begin[v + 1] - ab, W = (d + 63) >> 6;
@@ -313,38 +300,38 @@ __global__ void __launch_bounds__(KIND == KC_SMALL ? KC_SMALL_THREADS : KC_LARGE
         if (GLOBAL) __threadfence();
         __syncthreads();
         if (!only_build) {
-            kc_word vsum = 0;   // the wave's share of the vertex total (the same in every lane)
+            cc_word vsum = 0;   // the wave's share of the vertex total (the same in every lane)
             if (k == 3) {
-                kc_word mine = 0;
+                cc_word mine = 0;
                 for (int32_t i = share * T + tid; i < d; i += split * T) {
                     int32_t ro[KC_ROWS] = {i * W, 0, 0, 0, 0, 0};
-                    const kc_word t = kc_walk<0, 1, MODE>(A, W, ro, i >> 6, c, cnt, S);   // (one row: nothing to hand down)
-                    if (MODE != KC_NONE && t) kc_credit<MODE>(c, cnt, S, i, t);
+                    const cc_word t = kc_walk<0, 1, MODE>(A, W, ro, i >> 6, c, cnt, S);   // (one row: nothing to hand down)
+                    if (MODE != CC_NONE && t) kc_credit<MODE>(c, cnt, S, i, t);
                     mine += t;
                 }
-                vsum = kc_wave_total(mine);
+                vsum = cc_wave_total(mine);
             } else {
                 for (int32_t i = share * nwaves + wv; i < d; i += split * nwaves) {   // (wave-uniform)
-                    kc_word mine = 0;
+                    cc_word mine = 0;
                     for (int32_t j = i + 1 + lane; j < d; j += 64) {
                         if (!((A[i * W + (j >> 6)] >> (j & 63)) & 1ull)) continue;
                         int32_t ro[KC_ROWS] = {i * W, j * W, 0, 0, 0, 0};
-                        const kc_word sub = kc_walk_from<2, MODE>(k - 4, A, W, ro, j >> 6, c, cnt, S);
-                        if (MODE != KC_NONE && sub) kc_credit<MODE>(c, cnt, S, j, sub);
+                        const cc_word sub = kc_walk_from<2, MODE>(k - 4, A, W, ro, j >> 6, c, cnt, S);
+                        if (MODE != CC_NONE && sub) kc_credit<MODE>(c, cnt, S, j, sub);
                         mine += sub;
                     }
-                    const kc_word tot = kc_wave_total(mine);
-                    if (MODE != KC_NONE && lane == 0 && tot) kc_credit<MODE>(c, cnt, S, i, tot);
+                    const cc_word tot = cc_wave_total(mine);
+                    if (MODE != CC_NONE && lane == 0 && tot) kc_credit<MODE>(c, cnt, S, i, tot);
                     vsum += tot;
                 }
             }
             total += vsum;
-            if (MODE != KC_NONE && lane == 0 && vsum) atomicAdd(&cnt[v], vsum);
-            if (MODE == KC_COUNTERS) {   // flush the counters (LDS: and leave them zero)
+            if (MODE != CC_NONE && lane == 0 && vsum) atomicAdd(&cnt[v], vsum);
+            if (MODE == CC_LOCAL) {   // flush the counters (LDS: and leave them zero)
                 if (GLOBAL) __threadfence();
                 __syncthreads();
                 for (int32_t j = tid; j < d; j += T) {
-                    const kc_word cv = GLOBAL ? __hip_atomic_load(&c[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : c[j];
+                    const cc_word cv = GLOBAL ? __hip_atomic_load(&c[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : c[j];
                     if (cv) {
                         if (!GLOBAL) c[j] = 0;
                         atomicAdd(&cnt[S[j]], cv);
@@ -355,25 +342,6 @@ __global__ void __launch_bounds__(KIND == KC_SMALL ? KC_SMALL_THREADS : KC_LARGE
         __syncthreads();   // everybody is done with the list and the matrix before they are overwritten
     }
     if (lane == 0 && total) atomicAdd(&out[KC_TOTAL], total);
-}
-
-// ------------------------------------------------------------------ finishing kernel
-// one thread per caller's id x: the count back through perm; the vertices with a count and the sum of the counts
-__global__ void __launch_bounds__(KC_THREADS) kc_finish_kernel(const kc_word* __restrict__ cnt, const int32_t* __restrict__ perm /* NULL: identity */, int64_t V,
-                                                               int64_t* __restrict__ cnt_out, kc_word* __restrict__ out) {
-    kc_word nz = 0, sum = 0;
-    for (int64_t x = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; x < V; x += (int64_t) gridDim.x * blockDim.x) {
-        const kc_word cv = cnt[perm ? perm[x] : x];
-        cnt_out[x] = (int64_t) cv;
-        nz += cv ? 1 : 0;
-        sum += cv;
-    }
-    nz = wave_sum(nz);
-    sum = wave_sum(sum);
-    if ((threadIdx.x & 63) == 0) {
-        if (nz) atomicAdd(&out[KC_NONZERO], nz);
-        if (sum) atomicAdd(&out[KC_SUM], sum);
-    }
 }
 
 // ------------------------------------------------------------------ host
@@ -392,28 +360,15 @@ static int kc_prepare(tcd_plan* p) {
     hipStream_t s = 0;
     gmx_ws_scope scope;
     wbuf<uint32_t> key;
-    wbuf<int32_t> val;
     wbuf<int64_t> below;
-    wbuf<char> tmp;
     const int nb = KC_CAP + 2;
-    if (key.alloc((size_t) V) || val.alloc((size_t) V) || below.alloc((size_t) nb)) {
-        const std::string why = gmx_last_error();
-        gmx_set_error("kclique: the sort of %lld vertices by list length needs %zu bytes of workspace: %s", (long long) V,
-                      2 * (size_t) V * sizeof(int32_t) + (size_t) nb * sizeof(int64_t), why.c_str());
-        return GMX_ERR_NOMEM;
+    size_t tb = 0;   // the sort's temporary storage, once the sort knows it
+    int rc = key.alloc((size_t) V) || below.alloc((size_t) nb) ? GMX_ERR_NOMEM : GMX_OK;
+    if (rc == GMX_OK) {
+        hipLaunchKernelGGL(kc_len_kernel, dim3(grid_for(V)), dim3(KC_THREADS), 0, s, (const int32_t*) p->up_begin.p, V, key.p);
+        rc = tcd_sort_by_key(key.p, (uint32_t*) p->kc_d.p, p->kc_vtx.p, V, (unsigned) gmx_bits_for(V + 1) /* d <= V - 1 */, s, &tb);
     }
-    hipLaunchKernelGGL(kc_len_kernel, dim3(grid_for(V)), dim3(KC_THREADS), 0, s, (const int32_t*) p->up_begin.p, V, key.p);
-    hipLaunchKernelGGL(iota_kernel, dim3(grid_for(V)), dim3(KC_THREADS), 0, s, val.p, V);
-    GMX_HIP(hipGetLastError());
-    size_t tb = 0;
-    const unsigned end_bit = (unsigned) gmx_bits_for(V + 1);   // d <= V - 1
-    GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, key.p, (uint32_t*) p->kc_d.p, val.p, p->kc_vtx.p, (size_t) V, 0u, end_bit, s));
-    if (tmp.alloc(tb)) {
-        const std::string why = gmx_last_error();
-        gmx_set_error("kclique: the sort of %lld vertices by list length needs %zu bytes of temporary storage: %s", (long long) V, tb, why.c_str());
-        return GMX_ERR_NOMEM;
-    }
-    GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, key.p, (uint32_t*) p->kc_d.p, val.p, p->kc_vtx.p, (size_t) V, 0u, end_bit, s));
+    GMX_CHECK(cc_sort_nomem(rc, "kclique", "list length", V, 2 * (size_t) V * sizeof(int32_t) + (size_t) nb * sizeof(int64_t), tb));
     hipLaunchKernelGGL(kc_below_kernel, dim3((nb + KC_THREADS - 1) / KC_THREADS), dim3(KC_THREADS), 0, s, (const int32_t*) p->kc_d.p, V, nb, below.p);
     GMX_HIP(hipGetLastError());
     p->kc_below.assign((size_t) nb, 0);
@@ -427,44 +382,37 @@ struct kc_launch {   // what every class's launch shares
     const int32_t* up_idx;
     const int32_t* list;
     int k, mode;
-    kc_word* cnt;
-    kc_word* out;
+    cc_word* cnt;
+    cc_word* out;
 };
 
 static int kc_launch_wave(const kc_launch& L, int64_t lo, int64_t hi, int only_build) {
     const int64_t n = hi - lo;
     const dim3 grid(grid_for(n, KC_WAVES, 256 * 8)), block(KC_WAVES * 64);
-    if (L.mode == KC_NONE)
-        hipLaunchKernelGGL(kc_wave_kernel<KC_NONE>, grid, block, 0, 0, L.up_begin, L.up_idx, L.list + lo, n, L.k, KC_ALONE, only_build, L.cnt, L.out);
-    else if (L.mode == KC_COUNTERS)
-        hipLaunchKernelGGL(kc_wave_kernel<KC_COUNTERS>, grid, block, 0, 0, L.up_begin, L.up_idx, L.list + lo, n, L.k, KC_ALONE, only_build, L.cnt, L.out);
-    else
-        hipLaunchKernelGGL(kc_wave_kernel<KC_PLAIN>, grid, block, 0, 0, L.up_begin, L.up_idx, L.list + lo, n, L.k, KC_ALONE, only_build, L.cnt, L.out);
-    GMX_HIP(hipGetLastError());
-    return GMX_OK;
+    return cc_with_mode(L.mode, [&](auto mode) -> int {
+        hipLaunchKernelGGL(kc_wave_kernel<decltype(mode)::value>, grid, block, 0, 0, L.up_begin, L.up_idx, L.list + lo, n, L.k, KC_ALONE, only_build, L.cnt, L.out);
+        GMX_HIP(hipGetLastError());
+        return GMX_OK;
+    });
 }
 
-template <int MODE, int KIND>
-static int kc_launch_block_as(const kc_launch& L, int64_t lo, int64_t hi, int threads, int max_grid, int max_split, int dmax, int only_build, kc_word* ws,
-                              int64_t ws_stride) {
+template <int KIND>
+static int kc_launch_block(const kc_launch& L, int64_t lo, int64_t hi, int threads, int max_grid, int max_split, int dmax, int only_build, cc_word* ws,
+                           int64_t ws_stride) {
     const int64_t n = hi - lo;
     // the shares of a vertex: as many as fill max_grid workgroups, at most max_split
     const int split = (int) std::max<int64_t>(1, std::min<int64_t>(max_split, max_grid / n));
     const int64_t items = n * split;
     const size_t lds = KIND == KC_GLOBAL ? 0 : kc_lds_bytes(dmax);
-    if (KIND == KC_LARGE)   // (above 64 KiB a kernel has to be told)
-        GMX_HIP(hipFuncSetAttribute((const void*) kc_block_kernel<MODE, KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    hipLaunchKernelGGL((kc_block_kernel<MODE, KIND>), dim3((unsigned) (items < max_grid ? items : max_grid)), dim3(threads), lds, 0, L.up_begin, L.up_idx, L.list + lo, n,
-                       split, L.k, dmax, only_build, ws, ws_stride, L.cnt, L.out);
-    GMX_HIP(hipGetLastError());
-    return GMX_OK;
-}
-template <int KIND>
-static int kc_launch_block(const kc_launch& L, int64_t lo, int64_t hi, int threads, int max_grid, int max_split, int dmax, int only_build, kc_word* ws,
-                           int64_t ws_stride) {
-    if (L.mode == KC_NONE) return kc_launch_block_as<KC_NONE, KIND>(L, lo, hi, threads, max_grid, max_split, dmax, only_build, ws, ws_stride);
-    if (L.mode == KC_COUNTERS) return kc_launch_block_as<KC_COUNTERS, KIND>(L, lo, hi, threads, max_grid, max_split, dmax, only_build, ws, ws_stride);
-    return kc_launch_block_as<KC_PLAIN, KIND>(L, lo, hi, threads, max_grid, max_split, dmax, only_build, ws, ws_stride);
+    return cc_with_mode(L.mode, [&](auto mode) -> int {
+        constexpr int MODE = decltype(mode)::value;
+        if (KIND == KC_LARGE)   // (above 64 KiB a kernel has to be told)
+            GMX_HIP(hipFuncSetAttribute((const void*) kc_block_kernel<MODE, KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        hipLaunchKernelGGL((kc_block_kernel<MODE, KIND>), dim3((unsigned) (items < max_grid ? items : max_grid)), dim3(threads), lds, 0, L.up_begin, L.up_idx,
+                           L.list + lo, n, split, L.k, dmax, only_build, ws, ws_stride, L.cnt, L.out);
+        GMX_HIP(hipGetLastError());
+        return GMX_OK;
+    });
 }
 
 extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64_t* cliques, gmx_stats_t* stats) {
@@ -482,15 +430,10 @@ extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64
     const int64_t batch_bytes = gmx_env_int("GMX_KCLIQUE_BATCH_BYTES", KC_BATCH_BYTES, 1, INT64_MAX);
     const bool plain = getenv("GMX_KCLIQUE_PLAIN") != nullptr;
     const bool phase_log = getenv("GMX_KCLIQUE_PHASES") != nullptr;
-    const int mode = !count_host ? KC_NONE : plain ? KC_PLAIN : KC_COUNTERS;
-    // E = 0 or self loops only: zeros, answered without a plan
-    int64_t real = 0;
-    GMX_CHECK(tcd_real_slots(g, &real));
-    if (real == 0) {
-        if (count_host) memset(count_host, 0, (size_t) V * sizeof(int64_t));
-        if (stats) stats->iterations = 1;
-        return GMX_OK;
-    }
+    const int mode = !count_host ? CC_NONE : plain ? CC_PLAIN : CC_LOCAL;
+    bool empty = false;
+    GMX_CHECK(cc_answer_empty(g, count_host, stats, &empty));
+    if (empty) return GMX_OK;
     // graph preprocessing (cached on the graph, shared with gmx_triangle_counting_directed, gmx_clustering and gmx_ktruss; outside the timed region)
     bool built = false;
     tcd_plan* p = nullptr;
@@ -508,38 +451,22 @@ extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64
     const int small_hi = cap < KC_SMALL_D ? cap : KC_SMALL_D;
     const int64_t p0 = below[k - 1], p1 = use_wave ? below[KC_WAVE_D + 1] : p0, p2 = below[small_hi + 1], p3 = below[cap + 1];
     const int64_t n_wave = p1 - p0, n_small = p2 - p1, n_large = p3 - p2, n_global = V - p3;
-    // the global class's batches: [first, last) of the list, every vertex in a slot as large as the batch's last one needs
-    struct kc_batch { int64_t lo, hi, stride; };
-    std::vector<kc_batch> batches;
+    // the global class's batches: every vertex in a slot as large as the batch's last one needs (d ascends along the list)
+    std::vector<cc_batch> batches;
     size_t ws_bytes = 0;
     if (n_global > 0) {
         std::vector<int32_t> dg((size_t) n_global);
         GMX_HIP(hipMemcpy(dg.data(), p->kc_d.p + p3, (size_t) n_global * sizeof(int32_t), hipMemcpyDeviceToHost));
         // (only without the degree order, which bounds d by sqrt(2 |UP'|) < 2^16: the kernels keep row offsets in 32 bits)
         GMX_REQUIRE(kc_ws_words(dg.back()) <= INT32_MAX, "kclique: an upper list of %d entries: its bit matrix needs 32-bit row offsets", (int) dg.back());
-        const int64_t budget_words = batch_bytes / (int64_t) sizeof(kc_word);
-        for (int64_t a = 0; a < n_global;) {
-            int64_t b = a + 1;   // (a vertex that alone exceeds the budget is a batch by itself)
-            while (b < n_global && (b + 1 - a) * kc_ws_words(dg[b]) <= budget_words) b++;
-            const int64_t stride = kc_ws_words(dg[b - 1]);
-            batches.push_back({p3 + a, p3 + b, stride});
-            ws_bytes = std::max(ws_bytes, (size_t) ((b - a) * stride) * sizeof(kc_word));
-            a = b;
-        }
+        ws_bytes = sizeof(cc_word) * (size_t) cc_plan_batches(p3, V, [&](int64_t i) { return kc_ws_words(dg[i - p3]); }, batch_bytes / (int64_t) sizeof(cc_word), &batches);
     }
     // the call's scratch: cnt in the plan's numbering, the array asked for, the sums, the global class's workspace
-    gmx_ws_scope scope;
-    dbuf<kc_word> cnt, out;
-    dbuf<int64_t> cnt_out;
-    wbuf<kc_word> ws;
-    const size_t scratch = (count_host ? 2 * (size_t) V * sizeof(int64_t) : 0) + KC_NCTR * sizeof(kc_word) + ws_bytes;
-    if (out.alloc(KC_NCTR) || (count_host && (cnt.alloc((size_t) V) || cnt_out.alloc((size_t) V))) || (ws_bytes && ws.alloc(ws_bytes / sizeof(kc_word)))) {
-        const std::string why = gmx_last_error();
-        gmx_set_error("kclique: the per-vertex scratch and the global class's matrices need %zu bytes: %s", scratch, why.c_str());
-        return GMX_ERR_NOMEM;
-    }
-    GMX_HIP(hipMemset(out.p, 0, KC_NCTR * sizeof(kc_word)));
-    const kc_launch L = {p->up_begin.p, p->up_idx.p, p->kc_vtx.p, (int) k, mode, cnt.p, out.p};
+    cc_scratch S;
+    GMX_CHECK(S.alloc(KC_NCTR, count_host != nullptr, 1, V, ws_bytes, "kclique: the per-vertex scratch and the global class's matrices need %zu bytes: %s"));
+    cc_word* const cnt = S.acc.p;
+    cc_word* const ws = (cc_word*) S.ws.p;
+    const kc_launch L = {p->up_begin.p, p->up_idx.p, p->kc_vtx.p, (int) k, mode, cnt, S.out.p};
     // a class's launch; under GMX_KCLIQUE_PHASES once more in front of it, stopping behind the matrix, to time that share
     auto timed = [&](int slot, auto&& launch) -> int {
         float tb = 0;
@@ -556,40 +483,28 @@ extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64
     };
     gmx_spans tm;
     GMX_CHECK(tm.begin(tm.KERNEL));
-    if (count_host) GMX_HIP(hipMemsetAsync(cnt.p, 0, (size_t) V * sizeof(kc_word), 0));
+    if (count_host) GMX_HIP(hipMemsetAsync(cnt, 0, (size_t) V * sizeof(cc_word), 0));
     if (n_wave > 0) GMX_CHECK(timed(2, [&](int only_build) -> int { return kc_launch_wave(L, p0, p1, only_build); }));
     if (n_small > 0)
         GMX_CHECK(timed(3, [&](int only_build) -> int { return kc_launch_block<KC_SMALL>(L, p1, p2, KC_SMALL_THREADS, KC_SMALL_GRID, KC_SMALL_SPLIT, KC_SMALL_D, only_build, nullptr, 0); }));
     if (n_large > 0)
         GMX_CHECK(timed(4, [&](int only_build) -> int { return kc_launch_block<KC_LARGE>(L, p2, p3, KC_LARGE_THREADS, KC_LARGE_GRID, KC_LARGE_SPLIT, KC_CAP, only_build, nullptr, 0); }));
-    for (const kc_batch& b : batches)
+    for (const cc_batch& b : batches)
         GMX_CHECK(timed(5, [&](int only_build) -> int {
-            GMX_HIP(hipMemsetAsync(ws.p, 0, (size_t) ((b.hi - b.lo) * b.stride) * sizeof(kc_word), 0));
-            return kc_launch_block<KC_GLOBAL>(L, b.lo, b.hi, KC_LARGE_THREADS, INT32_MAX, 1, 0, only_build, ws.p, b.stride);
+            GMX_HIP(hipMemsetAsync(ws, 0, (size_t) ((b.hi - b.lo) * b.stride) * sizeof(cc_word), 0));
+            return kc_launch_block<KC_GLOBAL>(L, b.lo, b.hi, KC_LARGE_THREADS, INT32_MAX, 1, 0, only_build, ws, b.stride);
         }));
     phase.begin();
     if (count_host) {
-        hipLaunchKernelGGL(kc_finish_kernel, dim3(grid_for(V)), dim3(KC_THREADS), 0, 0, (const kc_word*) cnt.p, (const int32_t*) p->perm.p, V, cnt_out.p, out.p);
+        hipLaunchKernelGGL(cc_finish_kernel, dim3(grid_for(V)), dim3(CC_THREADS), 0, 0, (const cc_word*) cnt, (const cc_word*) nullptr, (const int32_t*) p->perm.p, V,
+                           S.cnt_out.p, S.out.p + KC_NONZERO, S.out.p + KC_SUM);
         GMX_HIP(hipGetLastError());
     }
     phase.end(&ph_ms[6]);
-    GMX_CHECK(tm.end(tm.KERNEL));
-    GMX_CHECK(tm.begin(tm.D2H));
-    kc_word h[KC_NCTR];
-    GMX_HIP(hipMemcpy(h, out.p, sizeof(h), hipMemcpyDeviceToHost));
-    if (count_host) GMX_HIP(hipMemcpy(count_host, cnt_out.p, (size_t) V * sizeof(int64_t), hipMemcpyDeviceToHost));
-    GMX_CHECK(tm.end(tm.D2H));
-    GMX_CHECK(tm.finish(stats));
-    if (count_host && h[KC_SUM] != (kc_word) k * h[KC_TOTAL]) {
-        gmx_set_error("kclique: the counts sum to %llu, not to %d x %llu", h[KC_SUM], (int) k, h[KC_TOTAL]);
-        return GMX_ERR_HIP;
-    }
+    cc_word h[KC_NCTR];
+    GMX_CHECK(cc_read_back(tm, S, h, KC_NCTR, V, count_host, stats));
+    GMX_CHECK(cc_check("kclique", count_host != nullptr, h[KC_SUM], (int) k, h[KC_TOTAL], h[KC_NONZERO], p->E_up, stats));
     *cliques = (int64_t) h[KC_TOTAL];
-    if (stats) {
-        stats->iterations = 1;
-        stats->edges_examined = p->E_up;
-        stats->vertices_reached = count_host ? (int64_t) h[KC_NONZERO] : 0;
-    }
     if (phase_log)
         fprintf(stderr, "gmx kclique phases: plan %.3f ms, matrices %.3f ms, wave %.3f ms, small %.3f ms, large %.3f ms, global %.3f ms, finish %.3f ms\n",
                 ph_ms[0], ph_ms[1], ph_ms[2], ph_ms[3], ph_ms[4], ph_ms[5], ph_ms[6]);
@@ -597,12 +512,12 @@ extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64
         fprintf(stderr, "gmx kclique: plan V %lld E %lld up %lld order %s built %d classes_built %d; k %d cap %d counts %s; items %lld wave + %lld small + "
                         "%lld large + %lld global + %lld skipped; batches %zu cliques %llu\n",
                 (long long) p->V, (long long) p->E, (long long) p->E_up, p->ordered ? "degree" : "identity", built ? 1 : 0, classes_built ? 1 : 0, (int) k, cap,
-                mode == KC_NONE ? "none" : mode == KC_PLAIN ? "global" : "lds", (long long) n_wave, (long long) n_small, (long long) n_large, (long long) n_global,
+                cc_mode_word(mode), (long long) n_wave, (long long) n_small, (long long) n_large, (long long) n_global,
                 (long long) p0, batches.size(), h[KC_TOTAL]);
     return GMX_OK;
 }
 
 void gmx_touch_kclique() {
     hipFuncAttributes attr;
-    (void) hipFuncGetAttributes(&attr, (const void*) kc_wave_kernel<KC_COUNTERS>);
+    (void) hipFuncGetAttributes(&attr, (const void*) kc_wave_kernel<CC_LOCAL>);
 }

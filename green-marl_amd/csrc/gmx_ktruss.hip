@@ -4,6 +4,7 @@
 // The stored slots are read as gmx_clustering reads them, N(v) = { u != v : v -> u or u -> v is stored }, on the plan of
 // gmx_tcd.hip (cached on the graph, shared with gmx_triangle_counting_directed and gmx_clustering): perm and UP', every
 // undirected edge once in sorted rows.  The position of an edge in up_idx is its EDGE ID.  On the first call the plan gets
+// (tcd_plan_adjacency in gmx_tcd.hip, which gmx_squares calls as well)
 //   adjacency  nb_begin / nb_idx / nb_eid: row v = DOWN'(v) then UP'(v), which is sorted as it stands (all of DOWN' < v < all
 //              of UP'), with the edge id of every slot.  The id of an upper slot is its own position; the lower slots come
 //              from ONE stable sort of (w, position) over up_idx: the run of w lists the edges (x, w) by ascending x.
@@ -32,8 +33,6 @@
 #include "gmx_tcd_plan.h"
 #include "gmx_rowgroup.h"
 #include "gmx_frontier.h"
-
-#include <rocprim/rocprim.hpp>
 
 #define KT_THREADS BFS_THREADS
 #define KT_LANE 16           // support: a lane walks a shorter row of up to this many slots by itself.  NOT MEASURED
@@ -81,41 +80,6 @@ struct kt_state {
 
 __device__ __forceinline__ int32_t kt_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int kt_shard() { return (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (BFS_SHARDS - 1); }
-
-// ------------------------------------------------------------------ the plan's additions
-// begin[r] = the first of the n sorted keys that is >= r, r <= V
-__global__ void __launch_bounds__(KT_THREADS) kt_down_begin_kernel(const uint32_t* __restrict__ key, int64_t n, int64_t V, int32_t* __restrict__ begin) {
-    for (int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; r <= V; r += (int64_t) gridDim.x * blockDim.x) {
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t) key[mid] < r) lo = mid + 1; else hi = mid;
-        }
-        begin[r] = (int32_t) lo;
-    }
-}
-__global__ void __launch_bounds__(KT_THREADS) kt_nb_begin_kernel(const int32_t* __restrict__ down_begin, const int32_t* __restrict__ up_begin, int64_t V,
-                                                                 int32_t* __restrict__ nb_begin) {
-    for (int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; v <= V; v += (int64_t) gridDim.x * blockDim.x) nb_begin[v] = down_begin[v] + up_begin[v];
-}
-// entry j of the sorted (w, position) pairs is the lower slot (x, w) of row w, x = the row of the position in UP'; the
-// position itself is the upper slot of row x.  up_src[position] = x.
-__global__ void __launch_bounds__(KT_THREADS) kt_fill_kernel(const uint32_t* __restrict__ key, const int32_t* __restrict__ pos_of, int64_t U, int64_t V,
-                                                             const int32_t* __restrict__ up_begin, const int32_t* __restrict__ up_idx,
-                                                             const int32_t* __restrict__ down_begin, const int32_t* __restrict__ nb_begin,
-                                                             int32_t* __restrict__ nb_idx, int32_t* __restrict__ nb_eid, int32_t* __restrict__ up_src) {
-    for (int64_t j = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; j < U; j += (int64_t) gridDim.x * blockDim.x) {
-        const int32_t w = (int32_t) key[j], pos = pos_of[j];
-        const int32_t x = csr_row_of(up_begin, V, (uint32_t) pos);
-        const int64_t lower = (int64_t) nb_begin[w] + (j - down_begin[w]);
-        nb_idx[lower] = x;
-        nb_eid[lower] = pos;
-        const int64_t upper = (int64_t) nb_begin[x] + (down_begin[x + 1] - down_begin[x]) + (pos - up_begin[x]);
-        nb_idx[upper] = w;   // (= up_idx[pos])
-        nb_eid[upper] = pos;
-        up_src[pos] = x;
-    }
-}
 
 // ------------------------------------------------------------------ support
 // the shorter row of edge {a, b}, a < b (ties: a), as [*sb, *se), and the longer one as [*lb, *le)
@@ -465,57 +429,6 @@ __global__ void __launch_bounds__(KT_THREADS) kt_finish_kernel(const int32_t* __
 }
 
 // ------------------------------------------------------------------ host
-// the plan's additions, once per plan (declared in gmx_tcd_plan.h: gmx_squares.hip walks the same adjacency)
-int tcd_plan_adjacency(tcd_plan* p) {
-    if (p->kt_ready) return GMX_OK;
-    const int64_t V = p->V, U = p->E_up;
-    GMX_REQUIRE(2 * U <= INT32_MAX, "ktruss: %lld undirected edges: the symmetric adjacency needs 32-bit offsets", (long long) U);
-    const size_t bytes = ((size_t) V + 1 + 5 * (size_t) U) * sizeof(int32_t);
-    if (p->nb_begin.alloc((size_t) V + 1) || p->nb_idx.alloc(2 * (size_t) U) || p->nb_eid.alloc(2 * (size_t) U) || p->up_src.alloc((size_t) U)) {
-        const std::string why = gmx_last_error();
-        p->nb_begin.release();
-        p->nb_idx.release();
-        p->nb_eid.release();
-        p->up_src.release();
-        gmx_set_error("ktruss: the symmetric adjacency of %lld edges needs %zu bytes: %s", (long long) U, bytes, why.c_str());
-        return GMX_ERR_NOMEM;
-    }
-    hipStream_t s = 0;
-    gmx_ws_scope scope;
-    wbuf<uint32_t> key, key2;
-    wbuf<int32_t> pos, pos2, down_begin;
-    wbuf<char> tmp;
-    GMX_CHECK(key.alloc((size_t) U));
-    GMX_CHECK(key2.alloc((size_t) U));
-    GMX_CHECK(pos.alloc((size_t) U));
-    GMX_CHECK(pos2.alloc((size_t) U));
-    GMX_CHECK(down_begin.alloc((size_t) V + 1));
-    const uint32_t* sorted = key.p;
-    const int32_t* sorted_pos = pos.p;
-    if (U > 0) {
-        GMX_HIP(hipMemcpyAsync(key.p, p->up_idx.p, (size_t) U * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(iota_kernel, dim3(grid_for(U)), dim3(KT_THREADS), 0, s, pos.p, U);
-        GMX_HIP(hipGetLastError());
-        size_t tb = 0;
-        const unsigned end_bit = (unsigned) gmx_bits_for(V);
-        GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, key.p, key2.p, pos.p, pos2.p, (size_t) U, 0u, end_bit, s));
-        GMX_CHECK(tmp.alloc(tb));
-        GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, key.p, key2.p, pos.p, pos2.p, (size_t) U, 0u, end_bit, s));
-        sorted = key2.p;
-        sorted_pos = pos2.p;
-    }
-    hipLaunchKernelGGL(kt_down_begin_kernel, dim3(grid_for(V + 1)), dim3(KT_THREADS), 0, s, sorted, U, V, down_begin.p);
-    hipLaunchKernelGGL(kt_nb_begin_kernel, dim3(grid_for(V + 1)), dim3(KT_THREADS), 0, s, (const int32_t*) down_begin.p, (const int32_t*) p->up_begin.p, V,
-                       p->nb_begin.p);
-    if (U > 0)
-        hipLaunchKernelGGL(kt_fill_kernel, dim3(grid_for(U)), dim3(KT_THREADS), 0, s, sorted, sorted_pos, U, V, (const int32_t*) p->up_begin.p,
-                           (const int32_t*) p->up_idx.p, (const int32_t*) down_begin.p, (const int32_t*) p->nb_begin.p, p->nb_idx.p, p->nb_eid.p, p->up_src.p);
-    GMX_HIP(hipGetLastError());
-    GMX_HIP(hipStreamSynchronize(s));
-    p->kt_ready = true;
-    return GMX_OK;
-}
-
 extern "C" int gmx_ktruss(gmx_graph_t* g, int32_t* truss_host, int32_t* support_host, int32_t* max_truss, int64_t* num_edges, gmx_stats_t* stats_out) {
     GMX_REQUIRE(max_truss, "NULL max_truss");
     GMX_REQUIRE(g, "NULL graph");

@@ -4,9 +4,10 @@
 //
 // The stored slots are read as gmx_clustering reads them, N(v) = { u != v : v -> u or u -> v is stored }, on the plan of
 // gmx_tcd.hip (cached on the graph, shared with gmx_triangle_counting_directed, gmx_clustering, gmx_ktruss and gmx_kclique)
-// and the symmetric adjacency gmx_ktruss.hip adds to it: row v of nb_idx = DOWN'(v) then UP'(v), sorted.  A square is found
-// exactly once, at its highest plan id u, by the wedges u - v - w with v in DOWN'(u), w in N'(v), w < u: with c(w) the wedges
-// of u that end in w, the squares with top u and opposite vertex w number C(c(w), 2).
+// and the symmetric adjacency that tcd_plan_adjacency adds to it: row v of nb_idx = DOWN'(v) then UP'(v), sorted.  A square is
+// found exactly once, at its highest plan id u, by the wedges u - v - w with v in DOWN'(u), w in N'(v), w < u: with c(w) the
+// wedges of u that end in w, the squares with top u and opposite vertex w number C(c(w), 2).  The frame of the entry, the mode
+// dispatch, the batches and the finishing kernel are gmx_classcount.h's, shared with gmx_kclique.hip.
 //   additions  per DOWN' slot (u, v) the prefix length |{ w in N'(v) : w < u }| (one binary search), kept as the exclusive
 //              sums inside u's row, so that a row can be cut by wedges; W(u) = the wedges of u; the vertices by ascending W
 //              (one device sort; the vertices with fewer than two lower neighbours in front).
@@ -30,13 +31,7 @@
 // Every loop ends by construction (a row or a prefix is walked once; a probe sequence visits at most every slot of a table
 // that is at most half full); no kernel waits for another workgroup.  Integers only: every result is unique and the same
 // bytes under every knob.
-#include "gmx_tcd_plan.h"
-#include "gmx_rowgroup.h"
-#include "gmx_frontier.h"
-
-#include <rocprim/rocprim.hpp>
-
-#include <algorithm>
+#include "gmx_classcount.h"
 
 #define SQ_THREADS 256
 #define SQ_WAVES 4                    // waves of a wave-class workgroup
@@ -56,10 +51,7 @@
 #define SQ_ALONE 16                   // a lane walks a prefix of up to this many entries by itself.  Taken over from gmx_kclique.hip's KC_ALONE.  NOT MEASURED
 #define SQ_EMPTY (-1)                 // a free table slot (no plan id)
 
-typedef unsigned long long sq_word;
-
 enum { SQ_TOTAL, SQ_TOTAL2, SQ_NONZERO, SQ_SUM, SQ_NCTR };   // squares = TOTAL + TOTAL2 / 2
-enum { SQ_NONE = 0, SQ_CREDIT = 1, SQ_PLAIN = 2 };          // MODE: where the per-vertex credits go
 enum { SQ_STEP_COUNT, SQ_STEP_CREDIT, SQ_STEP_ZERO };       // the launches of a global-class batch
 
 struct sq_graph {   // what every kernel reads of the plan
@@ -69,9 +61,6 @@ struct sq_graph {   // what every kernel reads of the plan
     const int32_t* excl;   // [|UP'|]: per DOWN' slot (u's row begins at nb_begin[u] - up_begin[u]) the wedges of the slots in front of it
     const uint32_t* W;     // [V]
 };
-
-// the wave's sum, the same in every lane
-__device__ __forceinline__ sq_word sq_wave_total(sq_word x) { return rg_first_lane(wave_sum(x)); }
 
 // open addressing in LDS, linear probing: key[S] (SQ_EMPTY: free) and cnt[S]; at most S / 2 distinct keys are inserted
 struct sq_hash {
@@ -117,8 +106,8 @@ __device__ __forceinline__ sq_vertex sq_vertex_of(const sq_graph& G, int32_t u) 
 // call this together (this one is wave wv): f(v, w) per wedge returns what the wedge adds to its slot's sum, g(v, sum) is
 // called once per slot with a sum that is not zero, by one lane.  Returns this lane's share of the sum over all the wedges.
 template <class F, class G>
-__device__ __forceinline__ sq_word sq_walk(const sq_graph& P, const sq_vertex& X, int32_t j0, int32_t j1, int wv, int nwaves, int lane, F f, G g) {
-    sq_word mine = 0;
+__device__ __forceinline__ cc_word sq_walk(const sq_graph& P, const sq_vertex& X, int32_t j0, int32_t j1, int wv, int nwaves, int lane, F f, G g) {
+    cc_word mine = 0;
     for (int32_t jc = j0 + wv * 64; jc < j1; jc += nwaves * 64) {   // (wave-uniform)
         const int32_t j = jc + lane;
         const bool act = j < j1;
@@ -130,7 +119,7 @@ __device__ __forceinline__ sq_word sq_walk(const sq_graph& P, const sq_vertex& X
         }
         const bool by_wave = len > SQ_ALONE;
         if (!by_wave) {   // (len == 0 where the lane has no slot)
-            sq_word s = 0;
+            cc_word s = 0;
             for (int32_t i = 0; i < len; i++) s += f(v, P.nb_idx[vb + i]);
             if (s) g(v, s);
             mine += s;
@@ -140,7 +129,7 @@ __device__ __forceinline__ sq_word sq_walk(const sq_graph& P, const sq_vertex& X
             const int src = __builtin_ctzll(m);
             m &= m - 1;
             const int32_t sv = __builtin_amdgcn_readlane(v, src), svb = __builtin_amdgcn_readlane(vb, src), slen = __builtin_amdgcn_readlane(len, src);
-            sq_word s = 0;
+            cc_word s = 0;
             for (int32_t i = lane; i < slen; i += 64) s += f(sv, P.nb_idx[svb + i]);
             mine += s;
             s = wave_sum(s);
@@ -152,11 +141,11 @@ __device__ __forceinline__ sq_word sq_walk(const sq_graph& P, const sq_vertex& X
 
 // pass 2's wedge: x = c(w) - 1 to w (PLAIN: to v and u as well, one atomic each)
 template <int MODE, class Table>
-__device__ __forceinline__ sq_word sq_credit_wedge(const Table& T, int32_t u, int32_t v, int32_t w, sq_word* __restrict__ mid, sq_word* __restrict__ end2) {
-    const sq_word x = (sq_word) (T.get(w) - 1);
+__device__ __forceinline__ cc_word sq_credit_wedge(const Table& T, int32_t u, int32_t v, int32_t w, cc_word* __restrict__ mid, cc_word* __restrict__ end2) {
+    const cc_word x = (cc_word) (T.get(w) - 1);
     if (x) {
         atomicAdd(&end2[w], x);
-        if (MODE == SQ_PLAIN) {
+        if (MODE == CC_PLAIN) {
             atomicAdd(&mid[v], x);
             atomicAdd(&end2[u], x);
         }
@@ -168,25 +157,25 @@ __device__ __forceinline__ sq_word sq_credit_wedge(const Table& T, int32_t u, in
 // landed for every wave that reads it).  Returns this lane's share of the total (NONE) or of the doubled total, and gives
 // u its share.
 template <int MODE, class Table, class Sync>
-__device__ __forceinline__ sq_word sq_vertex_passes(const sq_graph& P, const sq_vertex& X, const Table& T, int32_t j0, int32_t j1, int wv, int nwaves, int lane,
-                                                    sq_word* __restrict__ mid, sq_word* __restrict__ end2, Sync between) {
-    auto nothing = [](int32_t, sq_word) {};
-    if (MODE == SQ_NONE) return sq_walk(P, X, j0, j1, wv, nwaves, lane, [&](int32_t, int32_t w) { return (sq_word) T.add(w); }, nothing);
-    sq_walk(P, X, j0, j1, wv, nwaves, lane, [&](int32_t, int32_t w) { (void) T.add(w); return (sq_word) 0; }, nothing);
+__device__ __forceinline__ cc_word sq_vertex_passes(const sq_graph& P, const sq_vertex& X, const Table& T, int32_t j0, int32_t j1, int wv, int nwaves, int lane,
+                                                    cc_word* __restrict__ mid, cc_word* __restrict__ end2, Sync between) {
+    auto nothing = [](int32_t, cc_word) {};
+    if (MODE == CC_NONE) return sq_walk(P, X, j0, j1, wv, nwaves, lane, [&](int32_t, int32_t w) { return (cc_word) T.add(w); }, nothing);
+    sq_walk(P, X, j0, j1, wv, nwaves, lane, [&](int32_t, int32_t w) { (void) T.add(w); return (cc_word) 0; }, nothing);
     between();
     const int32_t u = X.u;
-    const sq_word mine = sq_walk(P, X, j0, j1, wv, nwaves, lane, [&](int32_t v, int32_t w) { return sq_credit_wedge<MODE>(T, u, v, w, mid, end2); },
-                                 [&](int32_t v, sq_word s) { if (MODE == SQ_CREDIT) atomicAdd(&mid[v], s); });
-    if (MODE == SQ_CREDIT) {
-        const sq_word own = sq_wave_total(mine);
+    const cc_word mine = sq_walk(P, X, j0, j1, wv, nwaves, lane, [&](int32_t v, int32_t w) { return sq_credit_wedge<MODE>(T, u, v, w, mid, end2); },
+                                 [&](int32_t v, cc_word s) { if (MODE == CC_LOCAL) atomicAdd(&mid[v], s); });
+    if (MODE == CC_LOCAL) {
+        const cc_word own = cc_wave_total(mine);
         if (lane == 0 && own) atomicAdd(&end2[u], own);
     }
     return mine;
 }
 
-__device__ __forceinline__ void sq_tally(sq_word mine, int mode, int lane, sq_word* __restrict__ out) {
+__device__ __forceinline__ void sq_tally(cc_word mine, int mode, int lane, cc_word* __restrict__ out) {
     mine = wave_sum(mine);
-    if (lane == 0 && mine) atomicAdd(&out[mode == SQ_NONE ? SQ_TOTAL : SQ_TOTAL2], mine);
+    if (lane == 0 && mine) atomicAdd(&out[mode == CC_NONE ? SQ_TOTAL : SQ_TOTAL2], mine);
 }
 
 // ------------------------------------------------------------------ the plan's additions
@@ -194,10 +183,10 @@ __device__ __forceinline__ void sq_tally(sq_word mine, int mode, int lane, sq_wo
 // with fewer than two lower neighbours, else W + 1; the wedges of the others summed
 __global__ void __launch_bounds__(SQ_THREADS) sq_prefix_kernel(const int32_t* __restrict__ nb_begin, const int32_t* __restrict__ nb_idx,
                                                                const int32_t* __restrict__ up_begin, int64_t V, int32_t* __restrict__ excl,
-                                                               uint32_t* __restrict__ W, uint32_t* __restrict__ key, sq_word* __restrict__ wedges) {
+                                                               uint32_t* __restrict__ W, uint32_t* __restrict__ key, cc_word* __restrict__ wedges) {
     const int lane = threadIdx.x & 63;
     const int64_t nwaves = (int64_t) gridDim.x * (SQ_THREADS / 64);
-    sq_word live = 0;
+    cc_word live = 0;
     for (int64_t u = (int64_t) blockIdx.x * (SQ_THREADS / 64) + (threadIdx.x >> 6); u < V; u += nwaves) {   // (wave-uniform)
         const int32_t rb = nb_begin[u], ub = up_begin[u];
         const int32_t D = nb_begin[u + 1] - rb - (up_begin[u + 1] - ub), pb = rb - ub;
@@ -229,12 +218,12 @@ __global__ void __launch_bounds__(SQ_THREADS) sq_prefix_kernel(const int32_t* __
 
 // ------------------------------------------------------------------ wave class
 template <int MODE>
-__global__ void __launch_bounds__(SQ_WAVES * 64) sq_wave_kernel(sq_graph P, const int32_t* __restrict__ list, int64_t n, sq_word* __restrict__ mid,
-                                                                sq_word* __restrict__ end2, sq_word* __restrict__ out) {
+__global__ void __launch_bounds__(SQ_WAVES * 64) sq_wave_kernel(sq_graph P, const int32_t* __restrict__ list, int64_t n, cc_word* __restrict__ mid,
+                                                                cc_word* __restrict__ end2, cc_word* __restrict__ out) {
     __shared__ int32_t s_key[SQ_WAVES][SQ_WAVE_SLOTS];
     __shared__ int32_t s_cnt[SQ_WAVES][SQ_WAVE_SLOTS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    sq_word total = 0;
+    cc_word total = 0;
     const int64_t nwaves = (int64_t) gridDim.x * SQ_WAVES;
     for (int64_t it = (int64_t) blockIdx.x * SQ_WAVES + wv; it < n; it += nwaves) {   // (wave-uniform)
         const sq_vertex X = sq_vertex_of(P, list[it]);
@@ -254,12 +243,12 @@ __global__ void __launch_bounds__(SQ_WAVES * 64) sq_wave_kernel(sq_graph P, cons
 // ------------------------------------------------------------------ block class
 template <int MODE>
 __global__ void __launch_bounds__(SQ_BLOCK_THREADS) sq_block_kernel(sq_graph P, const int32_t* __restrict__ list, int64_t n, uint32_t slots,
-                                                                    sq_word* __restrict__ mid, sq_word* __restrict__ end2, sq_word* __restrict__ out) {
+                                                                    cc_word* __restrict__ mid, cc_word* __restrict__ end2, cc_word* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sq_lds[];
     int32_t* key = (int32_t*) sq_lds;
     int32_t* cnt = key + slots;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    sq_word total = 0;
+    cc_word total = 0;
     for (int64_t it = blockIdx.x; it < n; it += gridDim.x) {   // (workgroup-uniform)
         const sq_vertex X = sq_vertex_of(P, list[it]);
         const uint32_t S = X.W > 32 ? 2 * X.W : 64;   // (W <= slots / 2, slots >= 64)
@@ -287,8 +276,8 @@ __host__ __device__ __forceinline__ int32_t sq_parts(int64_t W, int64_t D, int64
 // workgroup (b, part): vertex list[b], whose counters are ws[b * stride ...), all zero before the batch and after it
 template <int MODE, int STEP>
 __global__ void __launch_bounds__(SQ_BLOCK_THREADS) sq_global_kernel(sq_graph P, const int32_t* __restrict__ list, int64_t split, int32_t* __restrict__ ws,
-                                                                     int64_t ws_off, int64_t stride, sq_word* __restrict__ mid, sq_word* __restrict__ end2,
-                                                                     sq_word* __restrict__ out) {
+                                                                     int64_t ws_off, int64_t stride, cc_word* __restrict__ mid, cc_word* __restrict__ end2,
+                                                                     cc_word* __restrict__ out) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = SQ_BLOCK_THREADS / 64;
     const sq_vertex X = sq_vertex_of(P, list[blockIdx.x]);
     const int32_t parts = sq_parts(X.W, X.D, split), part = (int32_t) blockIdx.y;
@@ -298,46 +287,25 @@ __global__ void __launch_bounds__(SQ_BLOCK_THREADS) sq_global_kernel(sq_graph P,
     const int32_t j0 = part == 0 ? 0 : rg_lower_bound<false>(ex, 0, X.D, (int32_t) ((uint64_t) part * X.W / (uint32_t) parts));
     const int32_t j1 = part + 1 == parts ? X.D : rg_lower_bound<false>(ex, 0, X.D, (int32_t) ((uint64_t) (part + 1) * X.W / (uint32_t) parts));
     const sq_dense T = {ws + (ws_off + (int64_t) blockIdx.x) * stride};
-    auto nothing = [](int32_t, sq_word) {};
+    auto nothing = [](int32_t, cc_word) {};
     const int32_t u = X.u;
-    sq_word mine = 0;
+    cc_word mine = 0;
     if (STEP == SQ_STEP_COUNT) {
-        if (MODE == SQ_NONE)
-            mine = sq_walk(P, X, j0, j1, wv, nw, lane, [&](int32_t, int32_t w) { return (sq_word) T.add(w); }, nothing);
+        if (MODE == CC_NONE)
+            mine = sq_walk(P, X, j0, j1, wv, nw, lane, [&](int32_t, int32_t w) { return (cc_word) T.add(w); }, nothing);
         else
-            sq_walk(P, X, j0, j1, wv, nw, lane, [&](int32_t, int32_t w) { (void) T.add(w); return (sq_word) 0; }, nothing);
+            sq_walk(P, X, j0, j1, wv, nw, lane, [&](int32_t, int32_t w) { (void) T.add(w); return (cc_word) 0; }, nothing);
     } else if (STEP == SQ_STEP_CREDIT) {
         mine = sq_walk(P, X, j0, j1, wv, nw, lane, [&](int32_t v, int32_t w) { return sq_credit_wedge<MODE>(T, u, v, w, mid, end2); },
-                       [&](int32_t v, sq_word s) { if (MODE == SQ_CREDIT) atomicAdd(&mid[v], s); });
-        if (MODE == SQ_CREDIT) {
-            const sq_word own = sq_wave_total(mine);
+                       [&](int32_t v, cc_word s) { if (MODE == CC_LOCAL) atomicAdd(&mid[v], s); });
+        if (MODE == CC_LOCAL) {
+            const cc_word own = cc_wave_total(mine);
             if (lane == 0 && own) atomicAdd(&end2[u], own);
         }
     } else {
-        sq_walk(P, X, j0, j1, wv, nw, lane, [&](int32_t, int32_t w) { T.ctr[w] = 0; return (sq_word) 0; }, nothing);
+        sq_walk(P, X, j0, j1, wv, nw, lane, [&](int32_t, int32_t w) { T.ctr[w] = 0; return (cc_word) 0; }, nothing);
     }
     if (STEP != SQ_STEP_ZERO) sq_tally(mine, MODE, lane, out);
-}
-
-// ------------------------------------------------------------------ finishing kernel
-// one thread per caller's id x: the count back through perm; the vertices with a count and the sum of the counts
-__global__ void __launch_bounds__(SQ_THREADS) sq_finish_kernel(const sq_word* __restrict__ mid, const sq_word* __restrict__ end2,
-                                                               const int32_t* __restrict__ perm /* NULL: identity */, int64_t V, int64_t* __restrict__ cnt_out,
-                                                               sq_word* __restrict__ out) {
-    sq_word nz = 0, sum = 0;
-    for (int64_t x = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; x < V; x += (int64_t) gridDim.x * blockDim.x) {
-        const int64_t p = perm ? perm[x] : x;
-        const sq_word cv = mid[p] + (end2[p] >> 1);
-        cnt_out[x] = (int64_t) cv;
-        nz += cv ? 1 : 0;
-        sum += cv;
-    }
-    nz = wave_sum(nz);
-    sum = wave_sum(sum);
-    if ((threadIdx.x & 63) == 0) {
-        if (nz) atomicAdd(&out[SQ_NONZERO], nz);
-        if (sum) atomicAdd(&out[SQ_SUM], sum);
-    }
 }
 
 // ------------------------------------------------------------------ host
@@ -357,30 +325,18 @@ static int sq_prepare(tcd_plan* p) {
     hipStream_t s = 0;
     gmx_ws_scope scope;
     wbuf<uint32_t> key, key2;
-    wbuf<int32_t> val;
-    wbuf<sq_word> wedges;
-    wbuf<char> tmp;
-    if (key.alloc((size_t) V) || key2.alloc((size_t) V) || val.alloc((size_t) V) || wedges.alloc(1)) {
-        const std::string why = gmx_last_error();
-        gmx_set_error("squares: the sort of %lld vertices by their wedges needs %zu bytes of workspace: %s", (long long) V, 3 * (size_t) V * sizeof(int32_t) + sizeof(sq_word),
-                      why.c_str());
-        return GMX_ERR_NOMEM;
+    wbuf<cc_word> wedges;
+    size_t tb = 0;   // the sort's temporary storage, once the sort knows it
+    int rc = key.alloc((size_t) V) || key2.alloc((size_t) V) || wedges.alloc(1) ? GMX_ERR_NOMEM : GMX_OK;
+    if (rc == GMX_OK) {
+        GMX_HIP(hipMemsetAsync(wedges.p, 0, sizeof(cc_word), s));
+        hipLaunchKernelGGL(sq_prefix_kernel, dim3(grid_for(V, SQ_THREADS / 64, 256 * 16)), dim3(SQ_THREADS), 0, s, (const int32_t*) p->nb_begin.p,
+                           (const int32_t*) p->nb_idx.p, (const int32_t*) p->up_begin.p, V, p->sq_excl.p, p->sq_W.p, key.p, wedges.p);
+        rc = tcd_sort_by_key(key.p, key2.p, p->sq_vtx.p, V, 32u, s, &tb);
     }
-    GMX_HIP(hipMemsetAsync(wedges.p, 0, sizeof(sq_word), s));
-    hipLaunchKernelGGL(sq_prefix_kernel, dim3(grid_for(V, SQ_THREADS / 64, 256 * 16)), dim3(SQ_THREADS), 0, s, (const int32_t*) p->nb_begin.p,
-                       (const int32_t*) p->nb_idx.p, (const int32_t*) p->up_begin.p, V, p->sq_excl.p, p->sq_W.p, key.p, wedges.p);
-    hipLaunchKernelGGL(iota_kernel, dim3(grid_for(V)), dim3(SQ_THREADS), 0, s, val.p, V);
-    GMX_HIP(hipGetLastError());
-    size_t tb = 0;
-    GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, key.p, key2.p, val.p, p->sq_vtx.p, (size_t) V, 0u, 32u, s));
-    if (tmp.alloc(tb)) {
-        const std::string why = gmx_last_error();
-        gmx_set_error("squares: the sort of %lld vertices by their wedges needs %zu bytes of temporary storage: %s", (long long) V, tb, why.c_str());
-        return GMX_ERR_NOMEM;
-    }
-    GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, key.p, key2.p, val.p, p->sq_vtx.p, (size_t) V, 0u, 32u, s));
+    GMX_CHECK(cc_sort_nomem(rc, "squares", "their wedges", V, 3 * (size_t) V * sizeof(int32_t) + sizeof(cc_word), tb));
     p->sq_key.assign((size_t) V, 0);
-    sq_word h = 0;
+    cc_word h = 0;
     GMX_HIP(hipMemcpy(p->sq_key.data(), key2.p, (size_t) V * sizeof(uint32_t), hipMemcpyDeviceToHost));
     GMX_HIP(hipMemcpy(&h, wedges.p, sizeof(h), hipMemcpyDeviceToHost));
     p->sq_wedges = (int64_t) h;
@@ -392,58 +348,44 @@ struct sq_launch {   // what every class's launch shares
     sq_graph P;
     const int32_t* list;
     int mode;
-    sq_word* mid;
-    sq_word* end2;
-    sq_word* out;
+    cc_word* mid;
+    cc_word* end2;
+    cc_word* out;
 };
 
 static int sq_launch_wave(const sq_launch& L, int64_t lo, int64_t hi) {
     const int64_t n = hi - lo;
-    const dim3 grid(grid_for(n, SQ_WAVES, 256 * 8)), block(SQ_WAVES * 64);
-    if (L.mode == SQ_NONE)
-        hipLaunchKernelGGL(sq_wave_kernel<SQ_NONE>, grid, block, 0, 0, L.P, L.list + lo, n, L.mid, L.end2, L.out);
-    else if (L.mode == SQ_CREDIT)
-        hipLaunchKernelGGL(sq_wave_kernel<SQ_CREDIT>, grid, block, 0, 0, L.P, L.list + lo, n, L.mid, L.end2, L.out);
-    else
-        hipLaunchKernelGGL(sq_wave_kernel<SQ_PLAIN>, grid, block, 0, 0, L.P, L.list + lo, n, L.mid, L.end2, L.out);
-    GMX_HIP(hipGetLastError());
-    return GMX_OK;
+    return cc_with_mode(L.mode, [&](auto mode) -> int {
+        hipLaunchKernelGGL(sq_wave_kernel<decltype(mode)::value>, dim3(grid_for(n, SQ_WAVES, 256 * 8)), dim3(SQ_WAVES * 64), 0, 0, L.P, L.list + lo, n, L.mid, L.end2, L.out);
+        GMX_HIP(hipGetLastError());
+        return GMX_OK;
+    });
 }
 
-template <int MODE>
-static int sq_launch_block_as(const sq_launch& L, int64_t lo, int64_t hi, int slots) {
+static int sq_launch_block(const sq_launch& L, int64_t lo, int64_t hi, int slots) {
     const int64_t n = hi - lo;
     const size_t lds = (size_t) slots * 2 * sizeof(int32_t);
-    if (lds > 64 * 1024)   // (above 64 KiB a kernel has to be told)
-        GMX_HIP(hipFuncSetAttribute((const void*) sq_block_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    hipLaunchKernelGGL(sq_block_kernel<MODE>, dim3(grid_for(n, 1, 256 * 8)), dim3(SQ_BLOCK_THREADS), lds, 0, L.P, L.list + lo, n, (uint32_t) slots, L.mid, L.end2, L.out);
-    GMX_HIP(hipGetLastError());
-    return GMX_OK;
-}
-static int sq_launch_block(const sq_launch& L, int64_t lo, int64_t hi, int slots) {
-    if (L.mode == SQ_NONE) return sq_launch_block_as<SQ_NONE>(L, lo, hi, slots);
-    if (L.mode == SQ_CREDIT) return sq_launch_block_as<SQ_CREDIT>(L, lo, hi, slots);
-    return sq_launch_block_as<SQ_PLAIN>(L, lo, hi, slots);
+    return cc_with_mode(L.mode, [&](auto mode) -> int {
+        constexpr int MODE = decltype(mode)::value;
+        if (lds > 64 * 1024)   // (above 64 KiB a kernel has to be told)
+            GMX_HIP(hipFuncSetAttribute((const void*) sq_block_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        hipLaunchKernelGGL(sq_block_kernel<MODE>, dim3(grid_for(n, 1, 256 * 8)), dim3(SQ_BLOCK_THREADS), lds, 0, L.P, L.list + lo, n, (uint32_t) slots, L.mid, L.end2, L.out);
+        GMX_HIP(hipGetLastError());
+        return GMX_OK;
+    });
 }
 
 // one step of a batch over the list's [lo, hi), the batch's slots [off, off + hi - lo), `parts` workgroups a vertex at most
-template <int MODE>
-static int sq_launch_global_as(const sq_launch& L, int step, int64_t lo, int64_t hi, int64_t off, int parts, int64_t split, int32_t* ws, int64_t stride) {
-    if (hi <= lo) return GMX_OK;
-    const dim3 grid((unsigned) (hi - lo), (unsigned) parts), block(SQ_BLOCK_THREADS);
-    if (step == SQ_STEP_COUNT)
-        hipLaunchKernelGGL((sq_global_kernel<MODE, SQ_STEP_COUNT>), grid, block, 0, 0, L.P, L.list + lo, split, ws, off, stride, L.mid, L.end2, L.out);
-    else if (step == SQ_STEP_CREDIT)
-        hipLaunchKernelGGL((sq_global_kernel<MODE, SQ_STEP_CREDIT>), grid, block, 0, 0, L.P, L.list + lo, split, ws, off, stride, L.mid, L.end2, L.out);
-    else
-        hipLaunchKernelGGL((sq_global_kernel<MODE, SQ_STEP_ZERO>), grid, block, 0, 0, L.P, L.list + lo, split, ws, off, stride, L.mid, L.end2, L.out);
-    GMX_HIP(hipGetLastError());
-    return GMX_OK;
-}
 static int sq_launch_global(const sq_launch& L, int step, int64_t lo, int64_t hi, int64_t off, int parts, int64_t split, int32_t* ws, int64_t stride) {
-    if (L.mode == SQ_NONE) return sq_launch_global_as<SQ_NONE>(L, step, lo, hi, off, parts, split, ws, stride);
-    if (L.mode == SQ_CREDIT) return sq_launch_global_as<SQ_CREDIT>(L, step, lo, hi, off, parts, split, ws, stride);
-    return sq_launch_global_as<SQ_PLAIN>(L, step, lo, hi, off, parts, split, ws, stride);
+    if (hi <= lo) return GMX_OK;
+    return cc_with_mode(L.mode, [&](auto mode) -> int {
+        return cc_with_mode(step, [&](auto step_c) -> int {   // (three steps: the same ladder)
+            hipLaunchKernelGGL((sq_global_kernel<decltype(mode)::value, decltype(step_c)::value>), dim3((unsigned) (hi - lo), (unsigned) parts), dim3(SQ_BLOCK_THREADS), 0, 0,
+                               L.P, L.list + lo, split, ws, off, stride, L.mid, L.end2, L.out);
+            GMX_HIP(hipGetLastError());
+            return GMX_OK;
+        });
+    });
 }
 
 extern "C" int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares, gmx_stats_t* stats) {
@@ -461,15 +403,10 @@ extern "C" int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares
     const int64_t split = gmx_env_int("GMX_SQUARES_SPLIT", SQ_SPLIT, 1, INT64_MAX);
     const bool plain = getenv("GMX_SQUARES_PLAIN") != nullptr;
     const bool phase_log = getenv("GMX_SQUARES_PHASES") != nullptr;
-    const int mode = !count_host ? SQ_NONE : plain ? SQ_PLAIN : SQ_CREDIT;
-    // E = 0 or self loops only: zeros, answered without a plan
-    int64_t real = 0;
-    GMX_CHECK(tcd_real_slots(g, &real));
-    if (real == 0) {
-        if (count_host) memset(count_host, 0, (size_t) V * sizeof(int64_t));
-        if (stats) stats->iterations = 1;
-        return GMX_OK;
-    }
+    const int mode = !count_host ? CC_NONE : plain ? CC_PLAIN : CC_LOCAL;
+    bool empty = false;
+    GMX_CHECK(cc_answer_empty(g, count_host, stats, &empty));
+    if (empty) return GMX_OK;
     // graph preprocessing (cached on the graph, shared with the other entries on the plan; outside the timed region)
     bool built = false;
     tcd_plan* p = nullptr;
@@ -497,41 +434,27 @@ extern "C" int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares
     if (n_global > 0) {
         std::vector<int32_t> ug((size_t) n_global);
         GMX_HIP(hipMemcpy(ug.data(), p->sq_vtx.p + p2, (size_t) n_global * sizeof(int32_t), hipMemcpyDeviceToHost));
-        const int64_t budget_words = batch_bytes / (int64_t) sizeof(int32_t);
-        auto words = [](int64_t u) -> int64_t { return (std::max<int64_t>(u, 1) + 63) & ~(int64_t) 63; };
-        for (int64_t a = 0; a < n_global;) {
-            int64_t b = a + 1, stride = words(ug[a]);   // (a vertex that alone exceeds the budget is a batch by itself)
-            while (b < n_global && (b + 1 - a) * std::max(stride, words(ug[b])) <= budget_words) {
-                stride = std::max(stride, words(ug[b]));
-                b++;
-            }
-            int64_t m = b;   // W ascends along the list: the vertices to cut are a suffix
-            while (m > a && (int64_t) key[p2 + m - 1] - 1 > split) m--;
-            n_split += b - m;
-            batches.push_back({p2 + a, p2 + m, p2 + b, stride, sq_parts((int64_t) key[p2 + b - 1] - 1, INT32_MAX, split)});
-            ws_words = std::max(ws_words, (size_t) ((b - a) * stride));
-            a = b;
+        std::vector<cc_batch> cut;
+        ws_words = (size_t) cc_plan_batches(p2, V, [&](int64_t i) { return (std::max<int64_t>(ug[i - p2], 1) + 63) & ~(int64_t) 63; },
+                                            batch_bytes / (int64_t) sizeof(int32_t), &cut);
+        for (const cc_batch& b : cut) {
+            int64_t m = b.hi;   // W ascends along the list: the vertices to cut are a suffix
+            while (m > b.lo && (int64_t) key[m - 1] - 1 > split) m--;
+            n_split += b.hi - m;
+            batches.push_back({b.lo, m, b.hi, b.stride, sq_parts((int64_t) key[b.hi - 1] - 1, INT32_MAX, split)});
         }
     }
     // the call's scratch: the two accumulators in the plan's numbering, the array asked for, the sums, the global class's counters
-    gmx_ws_scope scope;
-    dbuf<sq_word> acc, out;
-    dbuf<int64_t> cnt_out;
-    wbuf<int32_t> ws;
-    const size_t scratch = (count_host ? 3 * (size_t) V * sizeof(int64_t) : 0) + SQ_NCTR * sizeof(sq_word) + ws_words * sizeof(int32_t);
-    if (out.alloc(SQ_NCTR) || (count_host && (acc.alloc(2 * (size_t) V) || cnt_out.alloc((size_t) V))) || (ws_words && ws.alloc(ws_words))) {
-        const std::string why = gmx_last_error();
-        gmx_set_error("squares: the per-vertex scratch and the global class's counters need %zu bytes: %s", scratch, why.c_str());
-        return GMX_ERR_NOMEM;
-    }
-    GMX_HIP(hipMemset(out.p, 0, SQ_NCTR * sizeof(sq_word)));
-    sq_word* mid = acc.p;
-    sq_word* end2 = acc.p ? acc.p + V : nullptr;
-    const sq_launch L = {{p->nb_begin.p, p->nb_idx.p, p->up_begin.p, p->sq_excl.p, p->sq_W.p}, p->sq_vtx.p, mode, mid, end2, out.p};
+    cc_scratch S;
+    GMX_CHECK(S.alloc(SQ_NCTR, count_host != nullptr, 2, V, ws_words * sizeof(int32_t), "squares: the per-vertex scratch and the global class's counters need %zu bytes: %s"));
+    cc_word* const mid = S.acc.p;
+    cc_word* const end2 = S.acc.p ? S.acc.p + V : nullptr;
+    int32_t* const ws = (int32_t*) S.ws.p;
+    const sq_launch L = {{p->nb_begin.p, p->nb_idx.p, p->up_begin.p, p->sq_excl.p, p->sq_W.p}, p->sq_vtx.p, mode, mid, end2, S.out.p};
     gmx_spans tm;
     GMX_CHECK(tm.begin(tm.KERNEL));
-    if (count_host) GMX_HIP(hipMemsetAsync(acc.p, 0, 2 * (size_t) V * sizeof(sq_word), 0));
-    if (ws_words) GMX_HIP(hipMemsetAsync(ws.p, 0, ws_words * sizeof(int32_t), 0));   // (once: every batch leaves its counters zero)
+    if (count_host) GMX_HIP(hipMemsetAsync(mid, 0, 2 * (size_t) V * sizeof(cc_word), 0));
+    if (ws_words) GMX_HIP(hipMemsetAsync(ws, 0, ws_words * sizeof(int32_t), 0));   // (once: every batch leaves its counters zero)
     phase.begin();
     if (n_wave > 0) GMX_CHECK(sq_launch_wave(L, p0, p1));
     phase.end(&ph_ms[1]);
@@ -541,36 +464,23 @@ extern "C" int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares
     phase.begin();
     for (const sq_batch& b : batches)
         for (int step = SQ_STEP_COUNT; step <= SQ_STEP_ZERO; step++) {
-            if (step == SQ_STEP_CREDIT && mode == SQ_NONE) continue;
-            GMX_CHECK(sq_launch_global(L, step, b.lo, b.mid, 0, 1, split, ws.p, b.stride));
-            GMX_CHECK(sq_launch_global(L, step, b.mid, b.hi, b.mid - b.lo, b.parts, split, ws.p, b.stride));
+            if (step == SQ_STEP_CREDIT && mode == CC_NONE) continue;
+            GMX_CHECK(sq_launch_global(L, step, b.lo, b.mid, 0, 1, split, ws, b.stride));
+            GMX_CHECK(sq_launch_global(L, step, b.mid, b.hi, b.mid - b.lo, b.parts, split, ws, b.stride));
         }
     phase.end(&ph_ms[3]);
     phase.begin();
     if (count_host) {
-        hipLaunchKernelGGL(sq_finish_kernel, dim3(grid_for(V)), dim3(SQ_THREADS), 0, 0, (const sq_word*) mid, (const sq_word*) end2, (const int32_t*) p->perm.p, V,
-                           cnt_out.p, out.p);
+        hipLaunchKernelGGL(cc_finish_kernel, dim3(grid_for(V)), dim3(CC_THREADS), 0, 0, (const cc_word*) mid, (const cc_word*) end2, (const int32_t*) p->perm.p, V,
+                           S.cnt_out.p, S.out.p + SQ_NONZERO, S.out.p + SQ_SUM);
         GMX_HIP(hipGetLastError());
     }
     phase.end(&ph_ms[4]);
-    GMX_CHECK(tm.end(tm.KERNEL));
-    GMX_CHECK(tm.begin(tm.D2H));
-    sq_word h[SQ_NCTR];
-    GMX_HIP(hipMemcpy(h, out.p, sizeof(h), hipMemcpyDeviceToHost));
-    if (count_host) GMX_HIP(hipMemcpy(count_host, cnt_out.p, (size_t) V * sizeof(int64_t), hipMemcpyDeviceToHost));
-    GMX_CHECK(tm.end(tm.D2H));
-    GMX_CHECK(tm.finish(stats));
-    const sq_word total = h[SQ_TOTAL] + h[SQ_TOTAL2] / 2;
-    if (count_host && h[SQ_SUM] != 4 * total) {
-        gmx_set_error("squares: the counts sum to %llu, not to 4 x %llu", h[SQ_SUM], total);
-        return GMX_ERR_HIP;
-    }
+    cc_word h[SQ_NCTR];
+    GMX_CHECK(cc_read_back(tm, S, h, SQ_NCTR, V, count_host, stats));
+    const cc_word total = h[SQ_TOTAL] + h[SQ_TOTAL2] / 2;
+    GMX_CHECK(cc_check("squares", count_host != nullptr, h[SQ_SUM], 4, total, h[SQ_NONZERO], p->sq_wedges, stats));
     *squares = (int64_t) total;
-    if (stats) {
-        stats->iterations = 1;
-        stats->edges_examined = p->sq_wedges;
-        stats->vertices_reached = count_host ? (int64_t) h[SQ_NONZERO] : 0;
-    }
     if (phase_log)
         fprintf(stderr, "gmx squares phases: plan %.3f ms, wave %.3f ms, block %.3f ms, global %.3f ms, finish %.3f ms\n", ph_ms[0], ph_ms[1], ph_ms[2], ph_ms[3],
                 ph_ms[4]);
@@ -578,12 +488,12 @@ extern "C" int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares
         fprintf(stderr, "gmx squares: plan V %lld E %lld up %lld order %s built %d adj_built %d classes_built %d; wave_max %lld lds_slots %d split %lld "
                         "batch_bytes %lld counts %s; items %lld wave + %lld block + %lld global (%lld split) + %lld skipped; wedges %lld batches %zu squares %llu\n",
                 (long long) p->V, (long long) p->E, (long long) p->E_up, p->ordered ? "degree" : "identity", built ? 1 : 0, adj_built ? 1 : 0, classes_built ? 1 : 0,
-                (long long) wave_max, lds_slots, (long long) split, (long long) batch_bytes, mode == SQ_NONE ? "none" : mode == SQ_PLAIN ? "global" : "lds",
+                (long long) wave_max, lds_slots, (long long) split, (long long) batch_bytes, cc_mode_word(mode),
                 (long long) n_wave, (long long) n_block, (long long) n_global, (long long) n_split, (long long) p0, (long long) p->sq_wedges, batches.size(), total);
     return GMX_OK;
 }
 
 void gmx_touch_squares() {
     hipFuncAttributes attr;
-    (void) hipFuncGetAttributes(&attr, (const void*) sq_wave_kernel<SQ_CREDIT>);
+    (void) hipFuncGetAttributes(&attr, (const void*) sq_wave_kernel<CC_LOCAL>);
 }

@@ -10,8 +10,10 @@
 // not depend on the vertex numbering, and the count runs on a renumbered copy.
 //
 // Plan (graph preprocessing: built on first use from the forward CSR alone, cached on the graph, outside kernel_ms; the struct is
-// in gmx_tcd_plan.h because gmx_clustering, gmx_ktruss and gmx_kclique share the plan and keep their additions with it; they get
-// it through tcd_plan_get, ask tcd_real_slots whether there is an edge at all, and scan their groups with tcd_group_offsets):
+// in gmx_tcd_plan.h because gmx_clustering, gmx_ktruss, gmx_kclique and gmx_squares share the plan and keep their additions with
+// it; they get it through tcd_plan_get, ask tcd_real_slots whether there is an edge at all, scan their groups with
+// tcd_group_offsets and sort their lists with tcd_sort_by_key; the symmetric adjacency that gmx_ktruss and gmx_squares walk
+// is built here as well, by tcd_plan_adjacency):
 //   N      the undirected simple neighbourhood: keys (s,d) and (d,s) of every slot with s != d, sorted, repeats dropped;
 //   perm   ascending |N(x)| (stable: ties by id), or the identity with GMX_TCD_NO_ORDER=1;
 //   OUT'   the forward rows renumbered and sorted, repeats and self loops kept (E entries);
@@ -81,18 +83,14 @@ __global__ void tcd_extract_kernel(const uint64_t* __restrict__ keys, int64_t V,
     }
 }
 
-// ascending |N(x)|, as tc_degkey_kernel does it on a CSR; deg[] keeps |N(x)| for gmx_clustering (key, id NULL: only that)
-__global__ void tcd_degkey_kernel(const int32_t* __restrict__ nbegin, int64_t V, uint32_t* __restrict__ key, int32_t* __restrict__ id,
-                                  int32_t* __restrict__ deg) {
+// ascending |N(x)|, as tc_degkey_kernel does it on a CSR; deg[] keeps |N(x)| for gmx_clustering (key NULL: only that)
+__global__ void tcd_degkey_kernel(const int32_t* __restrict__ nbegin, int64_t V, uint32_t* __restrict__ key, int32_t* __restrict__ deg) {
     int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t) gridDim.x * blockDim.x;
     for (; i < V; i += stride) {
         const uint32_t d = (uint32_t) nbegin[i + 1] - (uint32_t) nbegin[i];   // (N has up to 2 E < 2^32 entries: the offsets may wrap, the difference does not)
         deg[i] = (int32_t) d;   // (< V <= 2^31 - 1)
-        if (key) {
-            key[i] = d;
-            id[i] = (int32_t) i;
-        }
+        if (key) key[i] = d;
     }
 }
 
@@ -130,6 +128,41 @@ static __global__ void __launch_bounds__(TCD_THREADS) tcd_real_slots_kernel(cons
         n += idx[i] != csr_row_of(begin, V, (uint32_t) i) ? 1 : 0;
     n = wave_sum(n);
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(out, n);
+}
+
+// ---- the symmetric adjacency (tcd_plan_adjacency)
+// begin[r] = the first of the n sorted keys that is >= r, r <= V
+__global__ void __launch_bounds__(TCD_THREADS) tcd_down_begin_kernel(const uint32_t* __restrict__ key, int64_t n, int64_t V, int32_t* __restrict__ begin) {
+    for (int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; r <= V; r += (int64_t) gridDim.x * blockDim.x) {
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t) key[mid] < r) lo = mid + 1; else hi = mid;
+        }
+        begin[r] = (int32_t) lo;
+    }
+}
+__global__ void __launch_bounds__(TCD_THREADS) tcd_nb_begin_kernel(const int32_t* __restrict__ down_begin, const int32_t* __restrict__ up_begin, int64_t V,
+                                                                   int32_t* __restrict__ nb_begin) {
+    for (int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; v <= V; v += (int64_t) gridDim.x * blockDim.x) nb_begin[v] = down_begin[v] + up_begin[v];
+}
+// entry j of the sorted (w, position) pairs is the lower slot (x, w) of row w, x = the row of the position in UP'; the
+// position itself is the upper slot of row x.  up_src[position] = x.
+__global__ void __launch_bounds__(TCD_THREADS) tcd_fill_kernel(const uint32_t* __restrict__ key, const int32_t* __restrict__ pos_of, int64_t U, int64_t V,
+                                                               const int32_t* __restrict__ up_begin, const int32_t* __restrict__ up_idx,
+                                                               const int32_t* __restrict__ down_begin, const int32_t* __restrict__ nb_begin,
+                                                               int32_t* __restrict__ nb_idx, int32_t* __restrict__ nb_eid, int32_t* __restrict__ up_src) {
+    for (int64_t j = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; j < U; j += (int64_t) gridDim.x * blockDim.x) {
+        const int32_t w = (int32_t) key[j], pos = pos_of[j];
+        const int32_t x = csr_row_of(up_begin, V, (uint32_t) pos);
+        const int64_t lower = (int64_t) nb_begin[w] + (j - down_begin[w]);
+        nb_idx[lower] = x;
+        nb_eid[lower] = pos;
+        const int64_t upper = (int64_t) nb_begin[x] + (down_begin[x + 1] - down_begin[x]) + (pos - up_begin[x]);
+        nb_idx[upper] = w;   // (= up_idx[pos])
+        nb_eid[upper] = pos;
+        up_src[pos] = x;
+    }
 }
 
 // ------------------------------------------------------------------ count kernel
@@ -249,6 +282,21 @@ static int tcd_sort_keys(uint64_t* a, uint64_t* b, int64_t n, unsigned end_bit, 
     return GMX_OK;
 }
 
+int tcd_sort_by_key(const uint32_t* key, uint32_t* key_sorted, int32_t* val_sorted, int64_t n, unsigned end_bit, hipStream_t s, size_t* tmp_bytes) {
+    if (tmp_bytes) *tmp_bytes = 0;
+    wbuf<int32_t> val;
+    wbuf<char> tmp;
+    GMX_CHECK(val.alloc((size_t) n));
+    hipLaunchKernelGGL(iota_kernel, dim3(grid_for(n)), dim3(TCD_THREADS), 0, s, val.p, n);
+    GMX_HIP(hipGetLastError());
+    size_t tb = 0;
+    GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, key, key_sorted, val.p, val_sorted, (size_t) n, 0u, end_bit, s));
+    if (tmp_bytes) *tmp_bytes = tb;
+    GMX_CHECK(tmp.alloc(tb));
+    GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, key, key_sorted, val.p, val_sorted, (size_t) n, 0u, end_bit, s));
+    return GMX_OK;
+}
+
 template <template <typename> class Buf>
 int tcd_group_offsets(const int32_t* begin, int64_t V, dbuf<int64_t>* grp_off, hipStream_t s) {
     Buf<int64_t> groups;
@@ -321,12 +369,10 @@ static int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
     dbuf<int32_t>& perm = p->perm;
     GMX_CHECK(p->deg.alloc((size_t) V));
     {
-        wbuf<int32_t> nbegin, id, order;
+        wbuf<int32_t> nbegin, order;
         wbuf<uint32_t> key, key2;
-        wbuf<char> tmp;
         GMX_CHECK(nbegin.alloc((size_t) V + 1));
         if (ordered) {
-            GMX_CHECK(id.alloc((size_t) V));
             GMX_CHECK(order.alloc((size_t) V));
             GMX_CHECK(key.alloc((size_t) V));
             GMX_CHECK(key2.alloc((size_t) V));
@@ -334,13 +380,10 @@ static int tcd_build_plan(const gmx_graph* g, bool ordered, tcd_plan** out) {
         }
         hipLaunchKernelGGL(tcd_extract_kernel, dim3(grid_for(V + 1, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, (const uint64_t*) nkeys, V, n, (int64_t) 0, nbegin.p,
                            (int32_t*) nullptr);
-        hipLaunchKernelGGL(tcd_degkey_kernel, dim3(grid_for(V, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, (const int32_t*) nbegin.p, V, key.p, id.p, p->deg.p);
+        hipLaunchKernelGGL(tcd_degkey_kernel, dim3(grid_for(V, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, (const int32_t*) nbegin.p, V, key.p, p->deg.p);
         GMX_HIP(hipGetLastError());
         if (ordered) {
-            size_t tb = 0;
-            GMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, key.p, key2.p, id.p, order.p, (size_t) V, 0u, 32u, s));
-            GMX_CHECK(tmp.alloc(tb));
-            GMX_HIP(rocprim::radix_sort_pairs((void*) tmp.p, tb, key.p, key2.p, id.p, order.p, (size_t) V, 0u, 32u, s));
+            GMX_CHECK(tcd_sort_by_key(key.p, key2.p, order.p, V, 32u, s));
             hipLaunchKernelGGL(tc_invert_kernel, dim3(grid_for(V, TCD_THREADS, 256 * 16)), dim3(TCD_THREADS), 0, s, (const int32_t*) order.p, V, perm.p);
             GMX_HIP(hipGetLastError());
         }
@@ -404,6 +447,46 @@ int tcd_real_slots(const gmx_graph* g, int64_t* real) {
         GMX_HIP(hipMemcpy(&h, cnt.p, sizeof(h), hipMemcpyDeviceToHost));
         *real = (int64_t) h;
     }
+    return GMX_OK;
+}
+
+// the plan's additions for gmx_ktruss and gmx_squares, once per plan (the error texts name the entry that had them first)
+int tcd_plan_adjacency(tcd_plan* p) {
+    if (p->kt_ready) return GMX_OK;
+    const int64_t V = p->V, U = p->E_up;
+    GMX_REQUIRE(2 * U <= INT32_MAX, "ktruss: %lld undirected edges: the symmetric adjacency needs 32-bit offsets", (long long) U);
+    const size_t bytes = ((size_t) V + 1 + 5 * (size_t) U) * sizeof(int32_t);
+    if (p->nb_begin.alloc((size_t) V + 1) || p->nb_idx.alloc(2 * (size_t) U) || p->nb_eid.alloc(2 * (size_t) U) || p->up_src.alloc((size_t) U)) {
+        const std::string why = gmx_last_error();
+        p->nb_begin.release();
+        p->nb_idx.release();
+        p->nb_eid.release();
+        p->up_src.release();
+        gmx_set_error("ktruss: the symmetric adjacency of %lld edges needs %zu bytes: %s", (long long) U, bytes, why.c_str());
+        return GMX_ERR_NOMEM;
+    }
+    hipStream_t s = 0;
+    gmx_ws_scope scope;
+    wbuf<uint32_t> key, key2;
+    wbuf<int32_t> pos2, down_begin;
+    GMX_CHECK(key.alloc((size_t) U));
+    GMX_CHECK(key2.alloc((size_t) U));
+    GMX_CHECK(pos2.alloc((size_t) U));
+    GMX_CHECK(down_begin.alloc((size_t) V + 1));
+    if (U > 0) {
+        GMX_HIP(hipMemcpyAsync(key.p, p->up_idx.p, (size_t) U * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        GMX_CHECK(tcd_sort_by_key(key.p, key2.p, pos2.p, U, (unsigned) gmx_bits_for(V), s));
+    }
+    const uint32_t* sorted = key2.p;   // (U == 0: nobody reads it)
+    hipLaunchKernelGGL(tcd_down_begin_kernel, dim3(grid_for(V + 1)), dim3(TCD_THREADS), 0, s, sorted, U, V, down_begin.p);
+    hipLaunchKernelGGL(tcd_nb_begin_kernel, dim3(grid_for(V + 1)), dim3(TCD_THREADS), 0, s, (const int32_t*) down_begin.p, (const int32_t*) p->up_begin.p, V,
+                       p->nb_begin.p);
+    if (U > 0)
+        hipLaunchKernelGGL(tcd_fill_kernel, dim3(grid_for(U)), dim3(TCD_THREADS), 0, s, sorted, (const int32_t*) pos2.p, U, V, (const int32_t*) p->up_begin.p,
+                           (const int32_t*) p->up_idx.p, (const int32_t*) down_begin.p, (const int32_t*) p->nb_begin.p, p->nb_idx.p, p->nb_eid.p, p->up_src.p);
+    GMX_HIP(hipGetLastError());
+    GMX_HIP(hipStreamSynchronize(s));
+    p->kt_ready = true;
     return GMX_OK;
 }
 

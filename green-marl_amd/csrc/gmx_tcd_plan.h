@@ -1,6 +1,6 @@
 // gmx_tcd_plan.h -- the plan gmx_tcd.hip builds from the forward CSR and caches on the graph, and how gmx_lcc.hip (gmx_clustering),
 // gmx_ktruss.hip (gmx_ktruss), gmx_kclique.hip (gmx_kclique) and gmx_squares.hip (gmx_squares) get at it: the lookup, the
-// empty-graph probe, the group offsets, the symmetric adjacency.
+// empty-graph probe, the group offsets, the symmetric adjacency, the sort by a key.
 #ifndef GMX_TCD_PLAN_H_
 #define GMX_TCD_PLAN_H_
 
@@ -20,9 +20,9 @@ struct tcd_plan {
     int64_t hubs = 0;           // the `hubs` highest plan ids, a multiple of 64 ...
     dbuf<uint32_t> hub_bits;    // ... and UP' among them as a hubs x hubs bit matrix: row u - (V - hubs), bit w - (V - hubs)
     double hub_ms = 0;
-    // the symmetric adjacency, built by the first gmx_ktruss or gmx_squares call on the plan (tcd_plan_adjacency, in
-    // gmx_ktruss.hip) and freed with it: in plan ids, row v = DOWN'(v) then UP'(v) (sorted as it stands), with the edge id --
-    // the position in up_idx -- of every slot, and the lower end of every edge id
+    // the symmetric adjacency, built by the first gmx_ktruss or gmx_squares call on the plan (tcd_plan_adjacency) and freed
+    // with it: in plan ids, row v = DOWN'(v) then UP'(v) (sorted as it stands), with the edge id -- the position in up_idx --
+    // of every slot, and the lower end of every edge id
     bool kt_ready = false;
     dbuf<int32_t> nb_begin;     // [V + 1]
     dbuf<int32_t> nb_idx;       // [2 E_up]
@@ -50,8 +50,13 @@ int tcd_plan_get(gmx_graph* g, bool ordered, tcd_plan** out, bool* built);
 // *real = the forward slots of g that are no self loop when g has no plan yet (one kernel pass and a read-back), else the
 // plan's E_up: zero exactly when there is no edge at all, which an entry asks before it has a plan built
 int tcd_real_slots(const gmx_graph* g, int64_t* real);
-// In gmx_ktruss.hip: the plan's symmetric adjacency (nb_begin, nb_idx, nb_eid, up_src), built unless it is there (kt_ready)
+// the plan's symmetric adjacency (nb_begin, nb_idx, nb_eid, up_src), built unless it is there (kt_ready)
 int tcd_plan_adjacency(tcd_plan* p);
+// key_sorted[0, n) = key[0, n) ascending by the bits [0, end_bit), stable, and val_sorted[j] = where key_sorted[j] stood in
+// key: the sort of the plan's vertices (edges) by a size that every member of the family does once per plan.  The values
+// 0 .. n - 1 and rocPRIM's temporary storage come from the caller's workspace scope; enqueued on s.  *tmp_bytes (if asked
+// for) = that storage's size once it is known, 0 before: a caller with its own GMX_ERR_NOMEM texts can tell which allocation it was
+int tcd_sort_by_key(const uint32_t* key, uint32_t* key_sorted, int32_t* val_sorted, int64_t n, unsigned end_bit, hipStream_t s, size_t* tmp_bytes = nullptr);
 // grp_off[0 .. V] (allocated here) = exclusive scan of the rows' 64-slot groups, a row of d = begin[v + 1] - begin[v] >= 2
 // slots having ceil((d - 1) / 64); synchronises s.  Buf: where the temporaries come from, wbuf inside a workspace scope or
 // dbuf (defined in gmx_tcd.hip, which instantiates exactly these two explicitly: another Buf is a link error)
