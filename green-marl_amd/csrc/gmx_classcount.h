@@ -150,4 +150,14 @@ static inline int cc_check(const char* who, bool counts, cc_word sum, int m, cc_
     return GMX_OK;
 }
 
+// ------------------------------------------------------------------ the counts of one entry for another (gmx_graphlets.hip)
+// The walks of gmx_squares and gmx_kclique at their default thresholds on a plan the caller holds, the per-vertex words left
+// on the device in PLAN ids; mode as above (CC_NONE: the totals only, the word arrays may be NULL).  The callers zero their
+// words; the launches are enqueued on stream 0 and have run on return.  *classes_built: the entry's additions to the plan were
+// built by this call.
+// gmx_squares.hip: squares through v = mid[v] + end2[v] / 2; squares = total2[0] + total2[1] / 2.  The adjacency is there.
+int sq_count_into(tcd_plan* p, int mode, cc_word* mid, cc_word* end2, cc_word* total2, bool* classes_built);
+// gmx_kclique.hip: the k-cliques through v = cnt[v]; *total = their number
+int kc_count_into(tcd_plan* p, int k, int mode, cc_word* cnt, cc_word* total, bool* classes_built);
+
 #endif

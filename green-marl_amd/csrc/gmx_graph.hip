@@ -403,6 +403,7 @@ void gmx_warm_modules() {
     gmx_touch_ktruss();
     gmx_touch_kclique();
     gmx_touch_squares();
+    gmx_touch_graphlets();
     gmx_touch_louvain();
 }
 

@@ -436,6 +436,7 @@ void gmx_touch_bicc();
 void gmx_touch_ktruss();
 void gmx_touch_kclique();
 void gmx_touch_squares();
+void gmx_touch_graphlets();
 void gmx_touch_louvain();
 void gmx_warm_modules();   // once per process: load every translation unit's code object (see gmx_touch_*)
 

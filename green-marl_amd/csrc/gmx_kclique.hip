@@ -415,6 +415,81 @@ static int kc_launch_block(const kc_launch& L, int64_t lo, int64_t hi, int threa
     });
 }
 
+struct kc_classes {   // the classes of a call, as ranges of the list: [p0, p1) wave, [p1, p2) small, [p2, p3) large, [p3, V) global
+    int64_t p0 = 0, p1 = 0, p2 = 0, p3 = 0;
+    std::vector<cc_batch> batches;   // the global class's: every vertex in a slot as large as the batch's last one needs (d ascends along the list)
+    size_t ws_bytes = 0;
+};
+
+static int kc_classify(tcd_plan* p, int k, int cap, bool use_wave, int64_t batch_bytes, kc_classes* C) {
+    const int64_t V = p->V;
+    const std::vector<int64_t>& below = p->kc_below;
+    const int small_hi = cap < KC_SMALL_D ? cap : KC_SMALL_D;
+    const int64_t p0 = below[k - 1], p1 = use_wave ? below[KC_WAVE_D + 1] : p0, p2 = below[small_hi + 1], p3 = below[cap + 1];
+    const int64_t n_global = V - p3;
+    C->p0 = p0;
+    C->p1 = p1;
+    C->p2 = p2;
+    C->p3 = p3;
+    if (n_global > 0) {
+        std::vector<int32_t> dg((size_t) n_global);
+        GMX_HIP(hipMemcpy(dg.data(), p->kc_d.p + p3, (size_t) n_global * sizeof(int32_t), hipMemcpyDeviceToHost));
+        // (only without the degree order, which bounds d by sqrt(2 |UP'|) < 2^16: the kernels keep row offsets in 32 bits)
+        GMX_REQUIRE(kc_ws_words(dg.back()) <= INT32_MAX, "kclique: an upper list of %d entries: its bit matrix needs 32-bit row offsets", (int) dg.back());
+        C->ws_bytes = sizeof(cc_word) * (size_t) cc_plan_batches(p3, V, [&](int64_t i) { return kc_ws_words(dg[i - p3]); }, batch_bytes / (int64_t) sizeof(cc_word), &C->batches);
+    }
+    return GMX_OK;
+}
+
+// every class's launches; ws: the global class's workspace.  ph_ms[1 .. 5]: matrices, wave, small, large, global (GMX_KCLIQUE_PHASES)
+static int kc_run(const kc_launch& L, const kc_classes& C, cc_word* ws, bool phase_log, gmx_phase_clock* phase, float* ph_ms) {
+    // a class's launch; under GMX_KCLIQUE_PHASES once more in front of it, stopping behind the matrix, to time that share
+    auto timed = [&](int slot, auto&& launch) -> int {
+        float tb = 0;
+        if (phase_log) {
+            phase->begin();
+            GMX_CHECK(launch(1));
+            tb = phase->end(&ph_ms[1]);
+        }
+        phase->begin();
+        GMX_CHECK(launch(0));
+        const float t = phase->end();
+        ph_ms[slot] += t > tb ? t - tb : 0.f;
+        return GMX_OK;
+    };
+    if (C.p1 > C.p0) GMX_CHECK(timed(2, [&](int only_build) -> int { return kc_launch_wave(L, C.p0, C.p1, only_build); }));
+    if (C.p2 > C.p1)
+        GMX_CHECK(timed(3, [&](int only_build) -> int { return kc_launch_block<KC_SMALL>(L, C.p1, C.p2, KC_SMALL_THREADS, KC_SMALL_GRID, KC_SMALL_SPLIT, KC_SMALL_D, only_build, nullptr, 0); }));
+    if (C.p3 > C.p2)
+        GMX_CHECK(timed(4, [&](int only_build) -> int { return kc_launch_block<KC_LARGE>(L, C.p2, C.p3, KC_LARGE_THREADS, KC_LARGE_GRID, KC_LARGE_SPLIT, KC_CAP, only_build, nullptr, 0); }));
+    for (const cc_batch& b : C.batches)
+        GMX_CHECK(timed(5, [&](int only_build) -> int {
+            GMX_HIP(hipMemsetAsync(ws, 0, (size_t) ((b.hi - b.lo) * b.stride) * sizeof(cc_word), 0));
+            return kc_launch_block<KC_GLOBAL>(L, b.lo, b.hi, KC_LARGE_THREADS, INT32_MAX, 1, 0, only_build, ws, b.stride);
+        }));
+    return GMX_OK;
+}
+
+// gmx_kclique's count for another entry on the plan (gmx_classcount.h), at the default thresholds
+int kc_count_into(tcd_plan* p, int k, int mode, cc_word* cnt, cc_word* total, bool* classes_built) {
+    *classes_built = !p->kc_ready;
+    GMX_CHECK(kc_prepare(p));
+    kc_classes Cl;
+    GMX_CHECK(kc_classify(p, k, KC_CAP, true, KC_BATCH_BYTES, &Cl));
+    gmx_ws_scope scope;
+    wbuf<char> ws;
+    if (Cl.ws_bytes && ws.alloc(Cl.ws_bytes)) {
+        const std::string why = gmx_last_error();
+        gmx_set_error("kclique: the global class's matrices need %zu bytes: %s", Cl.ws_bytes, why.c_str());
+        return GMX_ERR_NOMEM;
+    }
+    static_assert(KC_TOTAL == 0, "total[] is the front of the sums");
+    const kc_launch L = {p->up_begin.p, p->up_idx.p, p->kc_vtx.p, k, mode, cnt, total};
+    gmx_phase_clock off;
+    float ph_ms[6] = {0, 0, 0, 0, 0, 0};
+    return kc_run(L, Cl, (cc_word*) ws.p, false, &off, ph_ms);
+}
+
 extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64_t* cliques, gmx_stats_t* stats) {
     GMX_REQUIRE(cliques, "NULL cliques");
     GMX_REQUIRE(k >= 3 && k <= KC_MAX_K, "kclique: k = %d is outside 3 .. %d", (int) k, KC_MAX_K);
@@ -446,54 +521,21 @@ extern "C" int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64
     GMX_CHECK(kc_prepare(p));
     phase.end(&ph_ms[0]);
 
-    // the classes, as ranges of the list
-    const std::vector<int64_t>& below = p->kc_below;
-    const int small_hi = cap < KC_SMALL_D ? cap : KC_SMALL_D;
-    const int64_t p0 = below[k - 1], p1 = use_wave ? below[KC_WAVE_D + 1] : p0, p2 = below[small_hi + 1], p3 = below[cap + 1];
-    const int64_t n_wave = p1 - p0, n_small = p2 - p1, n_large = p3 - p2, n_global = V - p3;
-    // the global class's batches: every vertex in a slot as large as the batch's last one needs (d ascends along the list)
-    std::vector<cc_batch> batches;
-    size_t ws_bytes = 0;
-    if (n_global > 0) {
-        std::vector<int32_t> dg((size_t) n_global);
-        GMX_HIP(hipMemcpy(dg.data(), p->kc_d.p + p3, (size_t) n_global * sizeof(int32_t), hipMemcpyDeviceToHost));
-        // (only without the degree order, which bounds d by sqrt(2 |UP'|) < 2^16: the kernels keep row offsets in 32 bits)
-        GMX_REQUIRE(kc_ws_words(dg.back()) <= INT32_MAX, "kclique: an upper list of %d entries: its bit matrix needs 32-bit row offsets", (int) dg.back());
-        ws_bytes = sizeof(cc_word) * (size_t) cc_plan_batches(p3, V, [&](int64_t i) { return kc_ws_words(dg[i - p3]); }, batch_bytes / (int64_t) sizeof(cc_word), &batches);
-    }
+    kc_classes Cl;
+    GMX_CHECK(kc_classify(p, (int) k, cap, use_wave, batch_bytes, &Cl));
+    const int64_t p0 = Cl.p0, n_wave = Cl.p1 - Cl.p0, n_small = Cl.p2 - Cl.p1, n_large = Cl.p3 - Cl.p2, n_global = V - Cl.p3;
+    const std::vector<cc_batch>& batches = Cl.batches;
+    const size_t ws_bytes = Cl.ws_bytes;
     // the call's scratch: cnt in the plan's numbering, the array asked for, the sums, the global class's workspace
     cc_scratch S;
     GMX_CHECK(S.alloc(KC_NCTR, count_host != nullptr, 1, V, ws_bytes, "kclique: the per-vertex scratch and the global class's matrices need %zu bytes: %s"));
     cc_word* const cnt = S.acc.p;
     cc_word* const ws = (cc_word*) S.ws.p;
     const kc_launch L = {p->up_begin.p, p->up_idx.p, p->kc_vtx.p, (int) k, mode, cnt, S.out.p};
-    // a class's launch; under GMX_KCLIQUE_PHASES once more in front of it, stopping behind the matrix, to time that share
-    auto timed = [&](int slot, auto&& launch) -> int {
-        float tb = 0;
-        if (phase_log) {
-            phase.begin();
-            GMX_CHECK(launch(1));
-            tb = phase.end(&ph_ms[1]);
-        }
-        phase.begin();
-        GMX_CHECK(launch(0));
-        const float t = phase.end();
-        ph_ms[slot] += t > tb ? t - tb : 0.f;
-        return GMX_OK;
-    };
     gmx_spans tm;
     GMX_CHECK(tm.begin(tm.KERNEL));
     if (count_host) GMX_HIP(hipMemsetAsync(cnt, 0, (size_t) V * sizeof(cc_word), 0));
-    if (n_wave > 0) GMX_CHECK(timed(2, [&](int only_build) -> int { return kc_launch_wave(L, p0, p1, only_build); }));
-    if (n_small > 0)
-        GMX_CHECK(timed(3, [&](int only_build) -> int { return kc_launch_block<KC_SMALL>(L, p1, p2, KC_SMALL_THREADS, KC_SMALL_GRID, KC_SMALL_SPLIT, KC_SMALL_D, only_build, nullptr, 0); }));
-    if (n_large > 0)
-        GMX_CHECK(timed(4, [&](int only_build) -> int { return kc_launch_block<KC_LARGE>(L, p2, p3, KC_LARGE_THREADS, KC_LARGE_GRID, KC_LARGE_SPLIT, KC_CAP, only_build, nullptr, 0); }));
-    for (const cc_batch& b : batches)
-        GMX_CHECK(timed(5, [&](int only_build) -> int {
-            GMX_HIP(hipMemsetAsync(ws, 0, (size_t) ((b.hi - b.lo) * b.stride) * sizeof(cc_word), 0));
-            return kc_launch_block<KC_GLOBAL>(L, b.lo, b.hi, KC_LARGE_THREADS, INT32_MAX, 1, 0, only_build, ws, b.stride);
-        }));
+    GMX_CHECK(kc_run(L, Cl, ws, phase_log, &phase, ph_ms));
     phase.begin();
     if (count_host) {
         hipLaunchKernelGGL(cc_finish_kernel, dim3(grid_for(V)), dim3(CC_THREADS), 0, 0, (const cc_word*) cnt, (const cc_word*) nullptr, (const int32_t*) p->perm.p, V,

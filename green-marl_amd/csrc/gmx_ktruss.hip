@@ -429,6 +429,14 @@ __global__ void __launch_bounds__(KT_THREADS) kt_finish_kernel(const int32_t* __
 }
 
 // ------------------------------------------------------------------ host
+// sup[e] = the triangles on edge id e, for every entry on a plan that has its adjacency (gmx_tcd_plan.h); enqueued on stream 0
+int kt_support_into(tcd_plan* p, int32_t* sup) {
+    hipLaunchKernelGGL(kt_support_kernel, dim3(grid_for(p->E_up)), dim3(KT_THREADS), 0, 0, (const int32_t*) p->nb_begin.p, (const int32_t*) p->nb_idx.p,
+                       (const int32_t*) p->up_src.p, (const int32_t*) p->up_idx.p, p->E_up, KT_LANE, sup);
+    GMX_HIP(hipGetLastError());
+    return GMX_OK;
+}
+
 extern "C" int gmx_ktruss(gmx_graph_t* g, int32_t* truss_host, int32_t* support_host, int32_t* max_truss, int64_t* num_edges, gmx_stats_t* stats_out) {
     GMX_REQUIRE(max_truss, "NULL max_truss");
     GMX_REQUIRE(g, "NULL graph");
@@ -506,7 +514,7 @@ extern "C" int gmx_ktruss(gmx_graph_t* g, int32_t* truss_host, int32_t* support_
     GMX_CHECK(tm.begin(tm.KERNEL));
     phase.begin();
     GMX_HIP(hipMemsetAsync(ctl.p, 0, sizeof(kt_ctl), 0));
-    hipLaunchKernelGGL(kt_support_kernel, dim3(gu), dim3(KT_THREADS), 0, 0, S.nb_begin, S.nb_idx, S.up_src, S.up_idx, U, KT_LANE, sup0.p);
+    GMX_CHECK(kt_support_into(p, sup0.p));
     hipLaunchKernelGGL(kt_sum_kernel, dim3(gu), dim3(KT_THREADS), 0, 0, (const int32_t*) sup0.p, U, ctl.p);
     GMX_HIP(hipGetLastError());
     phase.end(&ph_ms[1]);

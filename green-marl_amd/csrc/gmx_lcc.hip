@@ -308,14 +308,19 @@ __global__ void lcc_finish_kernel(const unsigned long long* __restrict__ tri, co
 
 // ------------------------------------------------------------------ host
 // the plan's additions: the work items of the UP' rows (once) and the bit matrix of the H highest ids (again when H changes)
-static int lcc_prepare(tcd_plan* p, int64_t H, bool* hub_built) {
-    hipStream_t s = 0;
-    const int64_t V = p->V;
+int lcc_plan_groups(tcd_plan* p) {
     if (!p->lcc_ready) {
-        GMX_CHECK(tcd_group_offsets<dbuf>(p->up_begin.p, V, &p->up_grp_off, s));
+        GMX_CHECK(tcd_group_offsets<dbuf>(p->up_begin.p, p->V, &p->up_grp_off, 0));
         p->hubs = 0;
         p->lcc_ready = true;
     }
+    return GMX_OK;
+}
+
+static int lcc_prepare(tcd_plan* p, int64_t H, bool* hub_built) {
+    hipStream_t s = 0;
+    const int64_t V = p->V;
+    GMX_CHECK(lcc_plan_groups(p));
     if (p->hubs != H) {
         const double t0 = gmx_tick::now();
         p->hub_bits.release();

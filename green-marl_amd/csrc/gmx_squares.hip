@@ -388,6 +388,88 @@ static int sq_launch_global(const sq_launch& L, int step, int64_t lo, int64_t hi
     });
 }
 
+// the thresholds of a call (gmx_squares: its knobs; sq_count_into: the defaults)
+struct sq_knobs {
+    int64_t wave_max = SQ_WAVE_MAX;
+    int lds_slots = SQ_LDS_SLOTS;
+    int64_t batch_bytes = SQ_BATCH_BYTES, split = SQ_SPLIT;
+};
+// the global class's batches: [lo, hi) of the list, every vertex with as many counters as the batch's highest id needs
+// (whole 256-byte lines); [mid, hi) are the vertices that are cut into up to `parts` workgroups
+struct sq_batch { int64_t lo, mid, hi, stride; int parts; };
+struct sq_classes {   // the classes of a call, as ranges of the list: [p0, p1) wave, [p1, p2) block, [p2, V) global
+    int64_t p0 = 0, p1 = 0, p2 = 0, n_split = 0;
+    std::vector<sq_batch> batches;
+    size_t ws_words = 0;   // int32 counters of the largest batch
+};
+
+// the classes under the thresholds K: key 0 = skipped, else W + 1
+static int sq_classify(tcd_plan* p, const sq_knobs& K, sq_classes* C) {
+    const int64_t V = p->V;
+    const std::vector<uint32_t>& key = p->sq_key;
+    auto below = [&](int64_t k) -> int64_t { return std::lower_bound(key.begin(), key.end(), (uint32_t) std::min<int64_t>(k, UINT32_MAX)) - key.begin(); };
+    const int64_t p0 = below(1), p1 = K.wave_max > 0 ? below(K.wave_max + 2) : p0, p2 = std::max(p1, below((int64_t) K.lds_slots / 2 + 2));
+    const int64_t n_global = V - p2;
+    C->p0 = p0;
+    C->p1 = p1;
+    C->p2 = p2;
+    if (n_global > 0) {
+        std::vector<int32_t> ug((size_t) n_global);
+        GMX_HIP(hipMemcpy(ug.data(), p->sq_vtx.p + p2, (size_t) n_global * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::vector<cc_batch> cut;
+        C->ws_words = (size_t) cc_plan_batches(p2, V, [&](int64_t i) { return (std::max<int64_t>(ug[i - p2], 1) + 63) & ~(int64_t) 63; },
+                                               K.batch_bytes / (int64_t) sizeof(int32_t), &cut);
+        for (const cc_batch& b : cut) {
+            int64_t m = b.hi;   // W ascends along the list: the vertices to cut are a suffix
+            while (m > b.lo && (int64_t) key[m - 1] - 1 > K.split) m--;
+            C->n_split += b.hi - m;
+            C->batches.push_back({b.lo, m, b.hi, b.stride, sq_parts((int64_t) key[b.hi - 1] - 1, INT32_MAX, K.split)});
+        }
+    }
+    return GMX_OK;
+}
+
+// every class's launches; ws: the global class's counters, all zero.  ph_ms[1 .. 3]: wave, block, global (GMX_SQUARES_PHASES)
+static int sq_run(const sq_launch& L, const sq_classes& C, const sq_knobs& K, int32_t* ws, gmx_phase_clock* phase, float* ph_ms) {
+    phase->begin();
+    if (C.p1 > C.p0) GMX_CHECK(sq_launch_wave(L, C.p0, C.p1));
+    phase->end(&ph_ms[1]);
+    phase->begin();
+    if (C.p2 > C.p1) GMX_CHECK(sq_launch_block(L, C.p1, C.p2, K.lds_slots));
+    phase->end(&ph_ms[2]);
+    phase->begin();
+    for (const sq_batch& b : C.batches)
+        for (int step = SQ_STEP_COUNT; step <= SQ_STEP_ZERO; step++) {
+            if (step == SQ_STEP_CREDIT && L.mode == CC_NONE) continue;
+            GMX_CHECK(sq_launch_global(L, step, b.lo, b.mid, 0, 1, K.split, ws, b.stride));
+            GMX_CHECK(sq_launch_global(L, step, b.mid, b.hi, b.mid - b.lo, b.parts, K.split, ws, b.stride));
+        }
+    phase->end(&ph_ms[3]);
+    return GMX_OK;
+}
+
+// gmx_squares' walk for another entry on the plan (gmx_classcount.h): the adjacency is there
+int sq_count_into(tcd_plan* p, int mode, cc_word* mid, cc_word* end2, cc_word* total2, bool* classes_built) {
+    *classes_built = !p->sq_ready;
+    GMX_CHECK(sq_prepare(p));
+    const sq_knobs K;
+    sq_classes Cl;
+    GMX_CHECK(sq_classify(p, K, &Cl));
+    gmx_ws_scope scope;
+    wbuf<int32_t> ws;
+    if (Cl.ws_words && ws.alloc(Cl.ws_words)) {
+        const std::string why = gmx_last_error();
+        gmx_set_error("squares: the global class's counters need %zu bytes: %s", Cl.ws_words * sizeof(int32_t), why.c_str());
+        return GMX_ERR_NOMEM;
+    }
+    if (Cl.ws_words) GMX_HIP(hipMemsetAsync(ws.p, 0, Cl.ws_words * sizeof(int32_t), 0));
+    static_assert(SQ_TOTAL == 0 && SQ_TOTAL2 == 1, "total2[] is the front of the sums");
+    const sq_launch L = {{p->nb_begin.p, p->nb_idx.p, p->up_begin.p, p->sq_excl.p, p->sq_W.p}, p->sq_vtx.p, mode, mid, end2, total2};
+    gmx_phase_clock off;
+    float ph_ms[4] = {0, 0, 0, 0};
+    return sq_run(L, Cl, K, ws.p, &off, ph_ms);
+}
+
 extern "C" int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares, gmx_stats_t* stats) {
     GMX_REQUIRE(squares, "NULL squares");
     GMX_REQUIRE(g, "NULL graph");
@@ -397,10 +479,11 @@ extern "C" int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares
     if (V == 0) return GMX_OK;
     // knobs, read at every call; no result byte depends on them
     const bool ordered = !getenv("GMX_SQUARES_NO_ORDER");
-    const int64_t wave_max = gmx_env_int("GMX_SQUARES_WAVE_MAX", SQ_WAVE_MAX, 0, SQ_WAVE_SLOTS / 2);
-    const int lds_slots = (int) gmx_env_int("GMX_SQUARES_LDS_SLOTS", SQ_LDS_SLOTS, SQ_LDS_SLOTS_MIN, SQ_LDS_SLOTS_MAX);
-    const int64_t batch_bytes = gmx_env_int("GMX_SQUARES_BATCH_BYTES", SQ_BATCH_BYTES, 1, INT64_MAX);
-    const int64_t split = gmx_env_int("GMX_SQUARES_SPLIT", SQ_SPLIT, 1, INT64_MAX);
+    sq_knobs K;
+    K.wave_max = gmx_env_int("GMX_SQUARES_WAVE_MAX", SQ_WAVE_MAX, 0, SQ_WAVE_SLOTS / 2);
+    K.lds_slots = (int) gmx_env_int("GMX_SQUARES_LDS_SLOTS", SQ_LDS_SLOTS, SQ_LDS_SLOTS_MIN, SQ_LDS_SLOTS_MAX);
+    K.batch_bytes = gmx_env_int("GMX_SQUARES_BATCH_BYTES", SQ_BATCH_BYTES, 1, INT64_MAX);
+    K.split = gmx_env_int("GMX_SQUARES_SPLIT", SQ_SPLIT, 1, INT64_MAX);
     const bool plain = getenv("GMX_SQUARES_PLAIN") != nullptr;
     const bool phase_log = getenv("GMX_SQUARES_PHASES") != nullptr;
     const int mode = !count_host ? CC_NONE : plain ? CC_PLAIN : CC_LOCAL;
@@ -420,30 +503,11 @@ extern "C" int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares
     GMX_CHECK(sq_prepare(p));
     phase.end(&ph_ms[0]);
 
-    // the classes, as ranges of the list: key 0 = skipped, else W + 1
-    const std::vector<uint32_t>& key = p->sq_key;
-    auto below = [&](int64_t k) -> int64_t { return std::lower_bound(key.begin(), key.end(), (uint32_t) std::min<int64_t>(k, UINT32_MAX)) - key.begin(); };
-    const int64_t p0 = below(1), p1 = wave_max > 0 ? below(wave_max + 2) : p0, p2 = std::max(p1, below((int64_t) lds_slots / 2 + 2));
-    const int64_t n_wave = p1 - p0, n_block = p2 - p1, n_global = V - p2;
-    // the global class's batches: [lo, hi) of the list, every vertex with as many counters as the batch's highest id needs
-    // (whole 256-byte lines); [mid, hi) are the vertices that are cut into up to `parts` workgroups
-    struct sq_batch { int64_t lo, mid, hi, stride; int parts; };
-    std::vector<sq_batch> batches;
-    size_t ws_words = 0;
-    int64_t n_split = 0;
-    if (n_global > 0) {
-        std::vector<int32_t> ug((size_t) n_global);
-        GMX_HIP(hipMemcpy(ug.data(), p->sq_vtx.p + p2, (size_t) n_global * sizeof(int32_t), hipMemcpyDeviceToHost));
-        std::vector<cc_batch> cut;
-        ws_words = (size_t) cc_plan_batches(p2, V, [&](int64_t i) { return (std::max<int64_t>(ug[i - p2], 1) + 63) & ~(int64_t) 63; },
-                                            batch_bytes / (int64_t) sizeof(int32_t), &cut);
-        for (const cc_batch& b : cut) {
-            int64_t m = b.hi;   // W ascends along the list: the vertices to cut are a suffix
-            while (m > b.lo && (int64_t) key[m - 1] - 1 > split) m--;
-            n_split += b.hi - m;
-            batches.push_back({b.lo, m, b.hi, b.stride, sq_parts((int64_t) key[b.hi - 1] - 1, INT32_MAX, split)});
-        }
-    }
+    sq_classes Cl;
+    GMX_CHECK(sq_classify(p, K, &Cl));
+    const int64_t p0 = Cl.p0, n_wave = Cl.p1 - Cl.p0, n_block = Cl.p2 - Cl.p1, n_global = V - Cl.p2, n_split = Cl.n_split;
+    const std::vector<sq_batch>& batches = Cl.batches;
+    const size_t ws_words = Cl.ws_words;
     // the call's scratch: the two accumulators in the plan's numbering, the array asked for, the sums, the global class's counters
     cc_scratch S;
     GMX_CHECK(S.alloc(SQ_NCTR, count_host != nullptr, 2, V, ws_words * sizeof(int32_t), "squares: the per-vertex scratch and the global class's counters need %zu bytes: %s"));
@@ -455,20 +519,7 @@ extern "C" int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares
     GMX_CHECK(tm.begin(tm.KERNEL));
     if (count_host) GMX_HIP(hipMemsetAsync(mid, 0, 2 * (size_t) V * sizeof(cc_word), 0));
     if (ws_words) GMX_HIP(hipMemsetAsync(ws, 0, ws_words * sizeof(int32_t), 0));   // (once: every batch leaves its counters zero)
-    phase.begin();
-    if (n_wave > 0) GMX_CHECK(sq_launch_wave(L, p0, p1));
-    phase.end(&ph_ms[1]);
-    phase.begin();
-    if (n_block > 0) GMX_CHECK(sq_launch_block(L, p1, p2, lds_slots));
-    phase.end(&ph_ms[2]);
-    phase.begin();
-    for (const sq_batch& b : batches)
-        for (int step = SQ_STEP_COUNT; step <= SQ_STEP_ZERO; step++) {
-            if (step == SQ_STEP_CREDIT && mode == CC_NONE) continue;
-            GMX_CHECK(sq_launch_global(L, step, b.lo, b.mid, 0, 1, split, ws, b.stride));
-            GMX_CHECK(sq_launch_global(L, step, b.mid, b.hi, b.mid - b.lo, b.parts, split, ws, b.stride));
-        }
-    phase.end(&ph_ms[3]);
+    GMX_CHECK(sq_run(L, Cl, K, ws, &phase, ph_ms));
     phase.begin();
     if (count_host) {
         hipLaunchKernelGGL(cc_finish_kernel, dim3(grid_for(V)), dim3(CC_THREADS), 0, 0, (const cc_word*) mid, (const cc_word*) end2, (const int32_t*) p->perm.p, V,
@@ -488,7 +539,7 @@ extern "C" int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares
         fprintf(stderr, "gmx squares: plan V %lld E %lld up %lld order %s built %d adj_built %d classes_built %d; wave_max %lld lds_slots %d split %lld "
                         "batch_bytes %lld counts %s; items %lld wave + %lld block + %lld global (%lld split) + %lld skipped; wedges %lld batches %zu squares %llu\n",
                 (long long) p->V, (long long) p->E, (long long) p->E_up, p->ordered ? "degree" : "identity", built ? 1 : 0, adj_built ? 1 : 0, classes_built ? 1 : 0,
-                (long long) wave_max, lds_slots, (long long) split, (long long) batch_bytes, cc_mode_word(mode),
+                (long long) K.wave_max, K.lds_slots, (long long) K.split, (long long) K.batch_bytes, cc_mode_word(mode),
                 (long long) n_wave, (long long) n_block, (long long) n_global, (long long) n_split, (long long) p0, (long long) p->sq_wedges, batches.size(), total);
     return GMX_OK;
 }

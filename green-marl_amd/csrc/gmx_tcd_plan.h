@@ -1,5 +1,5 @@
 // gmx_tcd_plan.h -- the plan gmx_tcd.hip builds from the forward CSR and caches on the graph, and how gmx_lcc.hip (gmx_clustering),
-// gmx_ktruss.hip (gmx_ktruss), gmx_kclique.hip (gmx_kclique) and gmx_squares.hip (gmx_squares) get at it: the lookup, the
+// gmx_ktruss.hip (gmx_ktruss), gmx_kclique.hip (gmx_kclique), gmx_squares.hip (gmx_squares) and gmx_graphlets.hip (gmx_graphlets) get at it: the lookup, the
 // empty-graph probe, the group offsets, the symmetric adjacency, the sort by a key.
 #ifndef GMX_TCD_PLAN_H_
 #define GMX_TCD_PLAN_H_
@@ -52,6 +52,12 @@ int tcd_plan_get(gmx_graph* g, bool ordered, tcd_plan** out, bool* built);
 int tcd_real_slots(const gmx_graph* g, int64_t* real);
 // the plan's symmetric adjacency (nb_begin, nb_idx, nb_eid, up_src), built unless it is there (kt_ready)
 int tcd_plan_adjacency(tcd_plan* p);
+// gmx_lcc.hip: the 64-slot groups of the UP' rows (up_grp_off), built unless they are there (lcc_ready): the work items of
+// gmx_clustering's walk and of gmx_graphlets' weighted one
+int lcc_plan_groups(tcd_plan* p);
+// gmx_ktruss.hip: sup[e] = the triangles on edge id e (kt_support_kernel), for an entry that keeps them on the device; the
+// adjacency is there; enqueued on stream 0
+int kt_support_into(tcd_plan* p, int32_t* sup);
 // key_sorted[0, n) = key[0, n) ascending by the bits [0, end_bit), stable, and val_sorted[j] = where key_sorted[j] stood in
 // key: the sort of the plan's vertices (edges) by a size that every member of the family does once per plan.  The values
 // 0 .. n - 1 and rocPRIM's temporary storage come from the caller's workspace scope; enqueued on s.  *tmp_bytes (if asked

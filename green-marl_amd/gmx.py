@@ -55,7 +55,7 @@ EXPORTS = [
     "gmx_graph_upload", "gmx_graph_from_edges", "gmx_graph_create_rmat", "gmx_graph_free", "gmx_graph_symmetrize",
     "gmx_graph_num_nodes", "gmx_graph_num_edges", "gmx_graph_download", "gmx_graph_edge_order",
     "gmx_graph_upload_e64", "gmx_graph_download_e64", "gmx_graph_edge_order_e64", "gmx_graph_reverse_edge_map_e64",
-    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_biconnected", "gmx_ktruss", "gmx_kclique", "gmx_squares", "gmx_louvain", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
+    "gmx_pagerank_f64", "gmx_pagerank_f32", "gmx_hop_dist", "gmx_bfs_levels", "gmx_bc", "gmx_bc_batch", "gmx_bc_all", "gmx_sssp", "gmx_sssp_path", "gmx_sssp_path_f64", "gmx_route_create", "gmx_route_free", "gmx_route_query", "gmx_bidir_dijkstra", "gmx_scc", "gmx_wcc", "gmx_kcore", "gmx_msf", "gmx_coloring", "gmx_closeness", "gmx_communities", "gmx_avg_teen_cnt", "gmx_conduct", "gmx_triangle_counting", "gmx_triangle_counting_part", "gmx_triangle_counting_cn", "gmx_triangle_counting_directed", "gmx_triangle_counting_directed_part", "gmx_clustering", "gmx_biconnected", "gmx_ktruss", "gmx_kclique", "gmx_squares", "gmx_graphlets", "gmx_louvain", "gmx_common_nbrs", "gmx_common_nbr_counts", "gmx_adamic_adar", "gmx_v_cover", "gmx_random_bipartite_matching", "gmx_random_walk_sampling", "gmx_node_sampling", "gmx_potential_friends", "gmx_graph_reverse_edge_map",
     "gmx_bfs_create", "gmx_bfs_free", "gmx_bfs_start", "gmx_bfs_step_begin", "gmx_bfs_found_bitmap", "gmx_bfs_step_end",
     "gmx_bfs_download",
     "gmx_pr_create", "gmx_pr_free", "gmx_pr_reset", "gmx_pr_step", "gmx_pr_contrib_slice",
@@ -153,6 +153,7 @@ def lib():
         L.gmx_ktruss.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_kclique.argtypes = [vp, i32, vp, C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_squares.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(Stats)]
+        L.gmx_graphlets.argtypes = [vp, C.c_int, vp, vp, C.POINTER(Stats)]
         L.gmx_louvain.argtypes = [vp, vp, i32, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(Stats)]
         L.gmx_bfs_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
         L.gmx_bfs_free.argtypes = [vp]
@@ -782,6 +783,20 @@ class Graph:
         n, st = C.c_int64(0), Stats()
         _ck(lib().gmx_squares(self._h, c.ctypes.data if per_vertex else None, C.byref(n), C.byref(st)))
         return (c[:V] if per_vertex else None, int(n.value), st.as_dict())
+
+    def graphlets(self, per_vertex=True, induced=True):
+        """The census of the connected subgraphs on 2, 3 and 4 vertices of the stored slots read as an undirected simple graph --
+        returns (gdv[int64, V x 15] or None, totals[int64, 9], stats).  gdv[v, k] is the number of subgraphs in which v sits at
+        orbit k (numbered as in ORCA: 0 degree, 1 - 2 path on 3, 3 triangle, 4 - 5 path on 4, 6 - 7 claw, 8 4-cycle, 9 - 11 paw,
+        12 - 13 diamond, 14 K4), totals[j] the number of graphlets G0 .. G8.  induced=True counts induced subgraphs,
+        induced=False subgraphs (the convention of squares(): gdv[:, 8] and gdv[:, 14] are squares()'s and kclique(4)'s
+        counts).  per_vertex=False is the cheap totals-only query: gdv is None and no per-vertex kernel runs.
+        stats["edges_examined"] is the number of triangles walked.  Forward CSR only, any row order (gmx.h: GMX_GRAPHLETS_*)."""
+        V = self.V
+        gdv = np.zeros((max(V, 1), 15), np.int64) if per_vertex else None
+        totals, st = np.zeros(9, np.int64), Stats()
+        _ck(lib().gmx_graphlets(self._h, 1 if induced else 0, gdv.ctypes.data if per_vertex else None, totals.ctypes.data, C.byref(st)))
+        return (gdv[:V] if per_vertex else None, totals, st.as_dict())
 
     def louvain(self, weight=None, max_levels=32, max_rounds=64):
         """Louvain modularity communities of the stored slots read as undirected edges -- returns (comm[int32], num_comms,

@@ -95,7 +95,7 @@ int gmx_workspace_release(void);
  * in whatever order their rows are, repeats apart from each other included; the validation pass records whether each
  * CSR's rows are sorted.  On such a graph:
  *   - gmx_pagerank_*, gmx_pr_*, gmx_hop_dist, gmx_bfs_*, gmx_bfs_levels, gmx_bc, gmx_bc_batch, gmx_bc_all, gmx_sssp, gmx_avg_teen_cnt, gmx_conduct,
- *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_clustering, gmx_kclique, gmx_squares, gmx_louvain, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
+ *     gmx_scc, gmx_wcc, gmx_kcore, gmx_msf, gmx_coloring, gmx_closeness, gmx_communities, gmx_potential_friends, gmx_triangle_counting_directed, gmx_triangle_counting_directed_part, gmx_clustering, gmx_kclique, gmx_squares, gmx_graphlets, gmx_louvain, gmx_v_cover, gmx_random_bipartite_matching, gmx_random_walk_sampling, gmx_node_sampling, gmx_sssp_path_f64, gmx_route_create / gmx_route_query / gmx_bidir_dijkstra and gmx_graph_symmetrize accept any row order and compute what the reference computes on the rows as
  *     stored (gmx_bc's float sums run in the stored slot order; gmx_sssp's len, gmx_sssp_path_f64's cost and prev_edge, the route entries' weight and path_edge, gmx_v_cover's select and gmx_msf's weight and in_forest are indexed by the stored slots);
  *   - gmx_triangle_counting, gmx_triangle_counting_part, gmx_triangle_counting_cn, gmx_common_nbrs,
  *     gmx_common_nbr_counts and gmx_adamic_adar binary-search rows, as the reference does on semi-sorted graphs only (shl_graph.cc:20,
@@ -953,6 +953,57 @@ int gmx_kclique(gmx_graph_t* g, int32_t k, int64_t* count_host, int64_t* cliques
  *                              and the finish, on stderr (tools/squares_prof.py).  It synchronises between the classes: take
  *                              kernel_ms from calls without this knob. */
 int gmx_squares(gmx_graph_t* g, int64_t* count_host, int64_t* squares, gmx_stats_t* stats);
+
+/* 4-node graphlet census and graphlet degree vectors (the reference has no such program): every connected subgraph on 2, 3
+ * and 4 vertices, in total and per vertex by orbit.  The stored slots are read exactly as gmx_clustering, gmx_ktruss, gmx_kclique
+ * and gmx_squares read them, N(v) = { u != v : v -> u or u -> v is stored }: self loops and repeated slots change nothing, rows
+ * may be in any order, and only the forward CSR is read (a GMX_GRAPH_NO_REVERSE graph works; there is no GMX_ERR_STATE).
+ * Graphlets and orbits, numbered as in ORCA:
+ *   G0 edge: 0 (the degree).   G1 path on 3: 1 end, 2 middle.   G2 triangle: 3.   G3 path on 4: 4 end, 5 inner.
+ *   G4 claw: 6 leaf, 7 centre.   G5 4-cycle: 8.   G6 paw (a triangle with a tail): 9 the tail's end, 10 the two triangle corners
+ *   away from the tail, 11 the corner that carries the tail.   G7 diamond (K4 minus an edge): 12 the two corners of degree 2, 13
+ *   the two of degree 3.   G8 K4: 14.
+ * induced = 1: gdv_host[v * 15 + k] (int64, row-major by the caller's vertex id) = the INDUCED subgraphs in which v sits at
+ * orbit k, and totals[0 .. 8] = the induced subgraphs of G0 .. G8.  induced = 0: the subgraph (non-induced) counts n_k, the
+ * convention of gmx_squares: gdv[v][8] is gmx_squares' count[v] and gdv[v][14] gmx_kclique's at k = 4, and totals counts
+ * subgraphs.  In either convention gdv[v][0] and gdv[v][3] are gmx_clustering's deg[v] and tri[v].  gdv_host may be NULL and is
+ * then neither built nor downloaded: the cheap totals-only query, which runs no per-vertex kernel (one pass over the edges, and
+ * the total-only modes of gmx_squares and gmx_kclique).  stats may be NULL.
+ * Arithmetic is in unsigned 64-bit words.  The induced counts are an integer-linear function of the n_k, so a wrap-around in an
+ * n_k is harmless: every returned number is exact whenever it fits an int64 itself (and gdv[v][8] while 2 * n8 < 2^64, as for
+ * gmx_squares).  C(x, 2) and C(d, 3) divide before they multiply (the even factor by two, the multiple of three by three), so
+ * that they do not wrap where the binomial fits: a star of 3.4 million leaves has d (d - 1) (d - 2) > 2^64 and C(d, 3) < 2^63.
+ * totals == NULL, induced outside {0, 1} or g == NULL (checked in this order, before g is touched): GMX_ERR_ARG before any device
+ * call.  V = 0: GMX_OK, nothing is written but totals = 0.  E = 0 or self loops only: GMX_OK, zeros, answered without a plan.
+ * When the scratch cannot be allocated: GMX_ERR_NOMEM, and the message gives the byte count.  Before it returns the entry
+ * verifies the sum identities of the orbits (sum o4 = sum o5, sum o6 = 3 sum o7, sum o9 = sum o11 = sum o10 / 2, sum o12 = sum
+ * o13, and the agreement with the triangles walked, the squares and the 4-cliques): a broken one is GMX_ERR_HIP with a text.
+ * Integers only: every result is unique and byte-identical from run to run and under every knob.
+ * Method: on the plan the counting family shares and its symmetric adjacency, in plan ids.  t(e), the
+ * triangles on every edge, from gmx_ktruss' support kernel; d from the rows, T(v) as half the sum of t(e) over v's row; two
+ * passes of row sums (sum (d_u - 1), sum C(d_u - 1, 2), sum t, sum t (d_u - 2), sum C(t, 2); then sum S(u) and sum T(u)); one
+ * weighted walk of the triangles that credits every corner with the support of the opposite edge minus one (orbit 12); the
+ * per-vertex words of gmx_squares and gmx_kclique at their default thresholds, kept on the device; a finishing kernel that
+ * forms the fifteen counts, applies the transform, sends the rows back through perm and sums the columns.
+ * stats: iterations = 1, edges_examined = the triangles walked (0 when gdv_host == NULL: there is no walk), vertices_reached =
+ * the vertices with a non-zero entry among the orbits 4 .. 14 of the rows returned (0 when gdv_host == NULL), kernel_ms = device
+ * time from the support kernel to the finish (the first call on a plan includes the additions of gmx_squares and gmx_kclique),
+ * d2h_ms = the downloads, h2d_ms = 0.
+ * Read at every call, no result byte depends on them:
+ *   GMX_GRAPHLETS_NO_ORDER=1   the plan keeps the graph's numbering;
+ *   GMX_GRAPHLETS_PLAIN=1      the walk as one work item per edge with one 64-bit global atomic per match (the form the default
+ *                              is measured against); the squares and the 4-cliques keep their default credits;
+ *   GMX_GRAPHLETS_CAP          list entries (and 32-bit counters) a wave stages in LDS, default 512, clamped to [64, 1024]; a
+ *                              longer list is searched in memory and credits by global atomics;
+ *   GMX_GRAPHLETS_LONG         default 2048, at least 1: a row of more slots is cut into 64-slot groups in the row passes;
+ *   GMX_GRAPHLETS_LOG=1        one line on stderr: `gmx graphlets: plan V <V> E <E> up <|UP'|> order <degree|identity> built <0|1>
+ *                              adj_built <0|1> groups_built <0|1> squares_built <0|1> kclique_built <0|1>; cap <n> long <n> counts
+ *                              <lds|global|none> induced <0|1>; items <a> staged + <b> memory; long_rows <n>; triangles <n>;
+ *                              totals <G0> ... <G8>` (no line when the call is answered without a plan);
+ *   GMX_GRAPHLETS_PHASES       the device time of the plan additions, the support kernel, the passes, the walk, the squares, the
+ *                              4-cliques and the finish, on stderr (tools/graphlets_prof.py).  It synchronises between them:
+ *                              take kernel_ms from calls without this knob. */
+int gmx_graphlets(gmx_graph_t* g, int induced, int64_t* gdv_host, int64_t* totals, gmx_stats_t* stats);
 
 /* Louvain modularity communities (the reference has no such program).  The graph is read as gmx_msf reads it: every stored
  * forward slot u -> w of weight x is an undirected edge; weight_host[E] is int32 by UPLOADED forward slot, NULL = every weight
